@@ -27,6 +27,10 @@ run on one GPU, and the end-to-end job (match -> tracks -> groups -> incremental
 bundle adjustment) on the 200-image set.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+
+`--dump-outputs DIR` writes what the last timed step returned (records and match lists of
+rank 0's pairs, see dump_outputs) so that two builds can be compared output for output: the
+image set is seeded, the same arguments give the same inputs.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -94,7 +98,47 @@ def parse():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo for rehearsal)")
     ap.add_argument("--exchange", default="shm", choices=["shm", "rccl"],
                     help="how the match lists reach rank 0 for N > 1: shared host segment (one node) or RCCL gather")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0's pairs) as DIR/<name>.npy, at most 64 MB")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config == 1:
+        ap.error("--dump-outputs belongs to the matching pass, not to the --config 1 plumbing run")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240901
+
+
+def dump_outputs(dir_path, out, budget=DUMP_BUDGET_BYTES):
+    """Writes the per-pair results of one pass (TwoViewMatching objects, in pair order) as .npy files:
+      pair_records.npy  (n, 6) float64: view_1_id, view_2_id, status, lowres_matches, num_matches, num_inliers
+      matches.npy       (rows, 2) float32: the lists of all matched pairs, concatenated in pair order
+                        (feature indices, exact in float32 below 2^24)
+    When the lists do not fit the budget, matches.npy holds a fixed seeded sample of their rows (in
+    order) and matches_rows.npy (float64) the index of each sampled row in the concatenation.
+    Returns {name: shape}."""
+    os.makedirs(dir_path, exist_ok=True)
+    rec = np.array([[tv.view_1_id, tv.view_2_id, tv.status, tv.lowres_matches, tv.num_matches, tv.num_inliers]
+                    for tv in out], dtype=np.float64).reshape(-1, 6)
+    lists = [np.asarray(tv.matches, dtype=np.int64).reshape(-1, 2) for tv in out]
+    allm = np.concatenate(lists) if lists else np.zeros((0, 2), np.int64)
+    if allm.size and (allm.min() < 0 or allm.max() >= 1 << 24):
+        raise ValueError("dump_outputs: feature index outside the exact float32 range")
+    files = {"pair_records": rec}
+    room = budget - rec.nbytes - 3 * 128                      # 128 bytes of .npy header per file
+    if allm.shape[0] * 8 <= room:
+        files["matches"] = allm.astype(np.float32)
+    else:
+        k = max(room // 16, 0)                                # 8 bytes of float32 row + 8 bytes of float64 index
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(allm.shape[0], size=k, replace=False))
+        files["matches"] = allm[rows].astype(np.float32)
+        files["matches_rows"] = rows.astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(dir_path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in files.items()}
 
 
 def launch_plan(argv, environ, gpus, single_process, config):
@@ -957,6 +1001,9 @@ def main():
     dt = time.perf_counter() - t0
     dt = D.max_over_ranks(dt, world, device=tdev)
     out = m.as_objects(last[0], last[1])          # the lists of the last timed pass, per pair
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, out)
     total_pairs = len(all_pairs)
     extras = rank == 0 and world == 1
 
@@ -1200,6 +1247,8 @@ def main():
                                           "workload": ba["workload"]}
         if e2e is not None:
             line["config3_single_gpu"] = e2e
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         print(json.dumps(line))
         if parity_bad:
             raise SystemExit(f"bench.py: GPU match lists differ from the oracle on pairs {parity_bad}")

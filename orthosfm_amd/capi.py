@@ -21,6 +21,10 @@ if not os.path.exists(LIB_PATH):
         "(hipcc --offload-arch=gfx950). orthosfm_amd has no CPU fallback.")
 
 lib = C.CDLL(LIB_PATH)
+# The HIP runtime the library is bound to, taken now: a torch imported later brings a second copy
+# of the runtime (same soname, another file), and a later CDLL("libamdhip64.so") returns that copy,
+# whose hipHostMalloc then reports no device.
+_hip = C.CDLL("libamdhip64.so")
 
 
 class OsfmError(RuntimeError):
@@ -193,10 +197,9 @@ def pinned_rows(rows: int):
     library is linked against), e.g. as the result buffer of HipExhaustiveMatching.compute: the
     match lists then leave the device at full PCIe rate instead of through pageable staging.
     Lives until pinned_free (or as long as the process)."""
-    hip = C.CDLL("libamdhip64.so")
     p = C.c_void_p()
     nbytes = max(int(rows), 1) * 8
-    rc = hip.hipHostMalloc(C.byref(p), C.c_size_t(nbytes), C.c_uint(0))
+    rc = _hip.hipHostMalloc(C.byref(p), C.c_size_t(nbytes), C.c_uint(0))
     if rc != 0 or not p.value:
         raise OsfmError(E_DEVICE, f"hipHostMalloc({nbytes}) failed with {rc}")
     buf = (C.c_int32 * (max(int(rows), 1) * 2)).from_address(p.value)
@@ -209,7 +212,7 @@ def pinned_free(arr) -> bool:
     addr = int(arr.ctypes.data)
     if _pinned_blocks.pop(addr, None) is None:
         return False
-    C.CDLL("libamdhip64.so").hipHostFree(C.c_void_p(addr))
+    _hip.hipHostFree(C.c_void_p(addr))
     return True
 
 

@@ -1,9 +1,9 @@
 """Generator of tests/golden/cfg1_suzanne.npz -- BASELINE configs[0], "3-image synthetic subset
-(Suzanne)".  Runs in the BUILD container only (it reads /root/reference, which does not exist on
-the GPU box); the .npz it writes is data: the landmark positions of the reference's own test model
-and the camera angles its test bench would draw.
+(Suzanne)".  Needs only g++ and what lies next to it; the .npz it writes is data: the landmark
+positions of the reference's own test model and the camera angles its test bench would draw.
 
-* points: the vertices of /root/reference/resources/Suzanne.ply, parsed the way
+* points: the vertices of the reference's resources/Suzanne.ply (stored here as the data fixture
+  suzanne.ply.gz, byte for byte the same file, gzipped), parsed the way
   orthosfm::loadPointClouds does (src/testbench/dataset_generation.cpp:96-137): every line behind
   "end_header", the first three blank-separated tokens through std::stod -> float64.  All 7872
   rows are kept, duplicates included (the exporter repeats a vertex per face): the test bench
@@ -17,6 +17,7 @@ and the camera angles its test bench would draw.
   with -- and print the values.  None of the reference's code is compiled or copied.
 BASELINE configs[0] uses the first three cameras.
 """
+import gzip
 import os
 import subprocess
 import sys
@@ -24,8 +25,8 @@ import tempfile
 
 import numpy as np
 
-REF = "/root/reference"
 HERE = os.path.dirname(os.path.abspath(__file__))
+PLY = os.path.join(HERE, "suzanne.ply.gz")
 
 CPP = r"""
 #include <cstdio>
@@ -49,7 +50,7 @@ int main() {
 def main():
     pts = []
     header = True
-    with open(os.path.join(REF, "resources", "Suzanne.ply")) as f:
+    with gzip.open(PLY, "rt") as f:
         for line in f:
             if header:
                 if line.startswith("end_header"):

@@ -154,3 +154,31 @@ def test_handoff_order_of_the_ba_kernels_in_the_isa():
     assert out.returncode == 0, out.stdout + out.stderr
     assert "chol_flow_kernel             scratch bytes 0" in out.stdout
     assert out.stdout.count("0 not behind a drained vmcnt") == 4 and "FAIL" not in out.stdout
+
+
+def test_pinned_rows_uses_the_hip_runtime_of_the_library_after_torch_is_imported():
+    """torch brings its own copy of the HIP runtime (same soname, another file).  Imported after the library, it
+    must not become the runtime pinned_rows allocates from: that copy was never initialised, and hipHostMalloc
+    there reports no device (a whole-suite run imports torch in test_distributed_cpu after the GPU tests of BA)."""
+    import subprocess
+    import sys
+    code = r'''
+import ctypes as C, sys
+sys.path.insert(0, sys.argv[1])
+def hip_files():
+    return {l.split()[-1] for l in open("/proc/self/maps") if "libamdhip64" in l}
+def owner(addr):
+    for l in open("/proc/self/maps"):
+        a, b = (int(x, 16) for x in l.split()[0].split("-"))
+        if a <= addr < b:
+            return l.split()[-1]
+from orthosfm_amd import capi
+bound = hip_files()
+import torch.distributed  # noqa: F401
+got = owner(C.cast(capi._hip.hipHostMalloc, C.c_void_p).value)
+print(len(bound), got in bound, len(hip_files()))
+'''
+    out = subprocess.run([sys.executable, "-s", "-c", code, ROOT], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    n_bound, same, _ = out.stdout.split()
+    assert n_bound == "1" and same == "True", out.stdout

@@ -1,6 +1,6 @@
 """tests/golden/cfg1_suzanne.npz (BASELINE configs[0]) is what its generator makes from the reference's
-resources/Suzanne.ply and the test bench's camera draw -- checked again here wherever the reference is
-present (the build container); everywhere else the committed fixture is checked for its shape."""
+resources/Suzanne.ply (kept beside it as tests/golden/suzanne.ply.gz) and the test bench's camera draw --
+checked again here by running the generator, and the fixture is checked for its shape."""
 import os
 import subprocess
 import sys
@@ -22,14 +22,12 @@ def test_fixture_shape():
 
 
 def test_fixture_equals_generator_output(tmp_path):
-    if not os.path.exists("/root/reference/resources/Suzanne.ply"):
-        import pytest
-        pytest.skip("reference not present (GPU box): the committed fixture stands")
-    # the generator writes next to itself: run a copy in a scratch folder
+    # the generator writes next to itself: run a copy (with the mesh it reads) in a scratch folder
     gen = os.path.join(HERE, "golden", "make_cfg1_suzanne.py")
     work = tmp_path / "golden"
     work.mkdir()
     (work / "make_cfg1_suzanne.py").write_text(open(gen).read())
+    (work / "suzanne.ply.gz").write_bytes(open(os.path.join(HERE, "golden", "suzanne.ply.gz"), "rb").read())
     subprocess.check_call([sys.executable, str(work / "make_cfg1_suzanne.py")], stdout=subprocess.DEVNULL)
     a, b = np.load(FIX), np.load(work / "cfg1_suzanne.npz")
     for k in ("points", "cams_deg", "width", "height"):
