@@ -93,6 +93,23 @@ OSFM_API int osfm_ba_debug_flow_spin_limit(int limit);
  * cameras' own order, chain in the order chosen, padding unknowns }.  blocks_capacity: rows `blocks` has room for. */
 OSFM_API int osfm_ba_debug_order(int num_cameras, const int32_t *cam_ldim, int num_pairs, const int32_t *pairs,
     int32_t *cam_off, uint64_t *blocks, int blocks_capacity, int32_t *info);
+/* Test hook (device 0): the dense Cholesky solve osfm_ba_solve runs on a reduced camera system of more than one block,
+ * applied to num_systems given systems A[r] x[r] = b[r] of order n (A: [num_systems][n][n], only the lower triangle
+ * is read; b, x: [num_systems][n]) one after the other on one stream, with ONE set of work arrays for the whole batch
+ * as in the LM loop: hand-off flags zeroed once and a new epoch per system, the factor's matrix filled with NaN once
+ * and never cleared.  n <= 32 is refused (those systems take a kernel of their own).
+ * num_cameras > 0: cam_ldim[num_cameras] unknowns per camera (summing to n) and pairs[num_pairs][2], the cameras that
+ * share a track: the elimination order osfm_ba_debug_order reports is looked for and, where one is chosen, the system
+ * is laid out in it (interior padding rows, block pattern) and x comes back in the caller's order.
+ * form 0: the form the solve would pick (the one-launch form where it fits), 1: launch per block column.  max_d /
+ * max_groups > 0 (form 0 only): D workgroups / workgroups of the one-launch launch for this call, in place of the
+ * defaults; OSFM_E_ARG when the one-launch form cannot run with them.  info[r]: the device's info word of system r
+ * as it is -- 0, the position of a pivot that is not positive (> 0), or >= 2^20 for a launch given up (not repeated
+ * here).  launch (may be NULL) [8] = { 1 one-launch form / 0 launch per column, its workgroups, D workgroups, P
+ * workgroups, P tiles, arcs of the elimination order (0: natural order), unknowns laid out (padding included), blocks of 32 }. */
+OSFM_API int osfm_ba_debug_cholesky_solve(int n, int num_systems, const double *A, const double *b, int num_cameras,
+    const int32_t *cam_ldim, int num_pairs, const int32_t *pairs, int form, int max_d, int max_groups, double *x,
+    int32_t *info, int32_t *launch);
 
 /* Diagnostic of the RANSAC-F scoring loop.  Its Sampson tests are pre-classified in packed
  * single precision; a test only counts when the float result is out of reach of its error

@@ -157,6 +157,33 @@ def solve(problem: FlatProblem, options: capi.BaOptions | None = None, **kw) -> 
     return s
 
 
+FORM_AS_SOLVE, FORM_PER_COLUMN = 0, 1
+_LAUNCH_FIELDS = ("one_launch", "groups", "num_d", "num_p", "num_tiles", "arcs", "span", "nblk")
+
+
+def debug_cholesky_solve(A, b, cam_ldim=None, pairs=None, form=FORM_AS_SOLVE, max_d=0, max_groups=0):
+    """osfm_ba_debug_cholesky_solve (test hook): the reduced system's dense Cholesky solve of osfm_ba_solve applied to
+    the batch A[r] x[r] = b[r] (A: (R, n, n), b: (R, n)), one system after the other on the same work arrays.
+    cam_ldim / pairs: the cameras' unknowns and the camera pairs that share a track -- the elimination order is
+    looked for as the solve does.  Returns (x (R, n), info (R,), launch: dict of _LAUNCH_FIELDS)."""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    if A.ndim == 2:
+        A, b = A[None], b.reshape(1, -1)
+    R, n = A.shape[0], A.shape[1]
+    if A.shape != (R, n, n) or b.shape != (R, n):
+        raise ValueError(f"A {A.shape} and b {b.shape} are not a batch of systems")
+    ldim = np.ascontiguousarray(cam_ldim if cam_ldim is not None else np.zeros(0), dtype=np.int32)
+    pr = np.ascontiguousarray(pairs if pairs is not None else np.zeros((0, 2)), dtype=np.int32).reshape(-1, 2)
+    x = np.empty((R, n))
+    info = np.zeros(R, dtype=np.int32)
+    launch = np.zeros(8, dtype=np.int32)
+    capi.check(capi.lib.osfm_ba_debug_cholesky_solve(
+        n, R, A, b, int(ldim.shape[0]), ldim.ctypes.data_as(C.c_void_p) if ldim.size else None,
+        int(pr.shape[0]), pr.ctypes.data_as(C.c_void_p) if pr.size else None, int(form), int(max_d), int(max_groups), x, info, launch))
+    return x, info, dict(zip(_LAUNCH_FIELDS, launch.tolist()))
+
+
 def reprojection_errors(problem: FlatProblem, device: int = 0):
     """Batched ReconstructionAlgorithm::evaluateReprojectionError."""
     O = problem.obs_camera.shape[0]

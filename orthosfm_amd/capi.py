@@ -129,6 +129,7 @@ class BaSummary(C.Structure):
 # every symbol include/osfm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "osfm_last_error", "osfm_version", "osfm_device_count", "osfm_device_memory", "osfm_library_memory", "osfm_trim_device_memory", "osfm_ransac_selfcheck", "osfm_ba_debug_chol_trace", "osfm_ba_debug_flow_spin_limit", "osfm_ba_debug_order",
+    "osfm_ba_debug_cholesky_solve",
     "osfm_match_options_default", "osfm_match_create", "osfm_match_create_multi", "osfm_match_get_devices", "osfm_match_destroy",
     "osfm_quantize_sift", "osfm_quantize_surf",
     "osfm_match_set_view", "osfm_match_set_view_float", "osfm_match_view_size", "osfm_match_expect_pairs", "osfm_match_set_positions",
@@ -162,6 +163,11 @@ if lib.osfm_version() != ABI_VERSION and os.environ.get("OSFM_ALLOW_ABI_MISMATCH
     raise ImportError(f"libosfm_hip.so reports ABI version {lib.osfm_version()}, orthosfm_amd/capi.py mirrors {ABI_VERSION} "
                       "(rebuild: make -C orthosfm_amd/csrc; experiments with an older build: OSFM_ALLOW_ABI_MISMATCH=1)")
 lib.osfm_device_count.restype = C.c_int
+_f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
+_i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
+lib.osfm_ba_debug_cholesky_solve.restype = C.c_int
+lib.osfm_ba_debug_cholesky_solve.argtypes = [C.c_int, C.c_int, _f64p, _f64p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_int, C.c_int, C.c_int, _f64p, _i32p, _i32p]
 
 
 def last_error() -> str:

@@ -604,6 +604,111 @@ int osfm_ba_debug_order(int num_cameras, const int32_t *cam_ldim, int num_pairs,
     return OSFM_OK;
 }
 
+int osfm_ba_debug_cholesky_solve(int n, int num_systems, const double *A, const double *b, int num_cameras, const int32_t *cam_ldim,
+    int num_pairs, const int32_t *pairs, int form, int max_d, int max_groups, double *x, int32_t *info, int32_t *launch)
+{
+    const char *what = "ba_debug_cholesky_solve";
+    if (n <= 32) { set_error("%s: n = %d: systems of one block are chol_small_kernel's, not this path's", what, n); return OSFM_E_ARG; }
+    if (n > 32 * 1024 || num_systems <= 0 || !A || !b || !x || !info) { set_error("%s: bad arguments", what); return OSFM_E_ARG; }
+    if (form != 0 && form != 1) { set_error("%s: form %d (0: as the solve picks, 1: launch per column)", what, form); return OSFM_E_ARG; }
+    if (max_d < 0 || max_groups < 0 || (form == 1 && (max_d || max_groups))) {
+        set_error("%s: max_d %d / max_groups %d (only the one-launch form has them)", what, max_d, max_groups); return OSFM_E_ARG;
+    }
+    if (num_cameras < 0 || num_pairs < 0 || (num_cameras && !cam_ldim) || (num_pairs && (!pairs || !num_cameras))) {
+        set_error("%s: bad camera arguments", what); return OSFM_E_ARG;
+    }
+    ReducedOrder ord;
+    if (num_cameras) {
+        int tot = 0;
+        for (int c = 0; c < num_cameras; ++c) {
+            if (cam_ldim[c] < 0) { set_error("%s: camera %d has %d unknowns", what, c, cam_ldim[c]); return OSFM_E_ARG; }
+            tot += cam_ldim[c];
+        }
+        if (tot != n) { set_error("%s: the cameras hold %d unknowns, the system %d", what, tot, n); return OSFM_E_ARG; }
+        std::vector<std::pair<int, int>> cp((size_t)num_pairs);
+        for (int i = 0; i < num_pairs; ++i) {
+            const int a = pairs[2 * i], c = pairs[2 * i + 1];
+            if (a < 0 || a >= num_cameras || c < 0 || c >= num_cameras) { set_error("%s: pair %d names camera %d / %d", what, i, a, c); return OSFM_E_ARG; }
+            cp[i] = {std::max(a, c), std::min(a, c)};
+        }
+        choose_reduced_order(num_cameras, cam_ldim, cp, &ord);
+    }
+    // the caller's unknown u sits at pos[u] of the laid-out system (ba_solve_core: cam_off), span unknowns in all
+    std::vector<int32_t> pos((size_t)n);
+    for (int u = 0; u < n; ++u) pos[u] = u;
+    if (ord.active)
+        for (int c = 0, u = 0; c < num_cameras; ++c)
+            for (int i = 0; i < cam_ldim[c]; ++i) pos[u++] = ord.cam_off[c] + i;
+    const int span = ord.active ? ord.span : n;
+    const int N = cholesky_padded_dim(span);
+    OSFM_RETURN_IF(select_device(0));
+    StreamGuard sg;
+    OSFM_RETURN_IF(sg.acquire());
+    hipStream_t s = sg.s;
+    DevArray ord_nz, ord_ptiles;
+    FlowPattern pattern;
+    if (ord.active) {
+        OSFM_RETURN_IF(upload(ord_nz, ord.nz.data(), ord.nz.size(), s));
+        OSFM_RETURN_IF(upload(ord_ptiles, ord.ptiles.data(), ord.ptiles.size(), s));
+        pattern.nz = ord_nz.as<unsigned long long>(); pattern.ptiles = ord_ptiles.as<int32_t>(); pattern.num_ptiles = (int)ord.ptiles.size();
+    }
+    const FlowPlan pl = chol_flow_plan(span, form == 0, pattern, max_d, max_groups);
+    if ((max_d || max_groups) && !pl.flow) {
+        set_error("%s: the one-launch form cannot run with max_d %d / max_groups %d (%d groups for %d D's, %d P's for %d tiles)",
+            what, max_d, max_groups, pl.groups, pl.num_d, pl.num_p, pl.num_tiles);
+        return OSFM_E_ARG;
+    }
+    // the buffers of ba_solve_core, one set for the whole batch: flags zeroed once, the factor's matrix filled with NaN
+    // once and never cleared again -- a tile read before its producer wrote it is the previous system's, or NaN
+    const size_t s_elems = (size_t)(N + 32) * N;
+    DevArray S, Lmat, Ldiag, xd, infod, flow_flags, flow_mailbox;
+    OSFM_RETURN_IF(S.alloc(s_elems * 8));
+    OSFM_RETURN_IF(Lmat.alloc(s_elems * 8));
+    OSFM_RETURN_IF(Ldiag.alloc((size_t)N * 32 * 8));
+    OSFM_RETURN_IF(xd.alloc((size_t)N * 8));
+    OSFM_RETURN_IF(infod.alloc((size_t)num_systems * 4));
+    OSFM_HIP_CHECK(hipMemsetAsync(Lmat.ptr, 0xff, s_elems * 8, s));
+    OSFM_HIP_CHECK(hipMemsetAsync(Ldiag.ptr, 0xff, (size_t)N * 32 * 8, s));
+    OSFM_HIP_CHECK(hipMemsetAsync(xd.ptr, 0xff, (size_t)N * 8, s));
+    OSFM_HIP_CHECK(hipMemsetAsync(infod.ptr, 0, (size_t)num_systems * 4, s));
+    if (form == 0) {
+        OSFM_RETURN_IF(flow_flags.alloc((size_t)chol_flow_flag_count(span) * 4));
+        OSFM_HIP_CHECK(hipMemsetAsync(flow_flags.ptr, 0, (size_t)chol_flow_flag_count(span) * 4, s));
+        OSFM_RETURN_IF(flow_mailbox.alloc(chol_flow_mailbox_bytes(span)));
+    }
+    // the laid-out system as the pair pass leaves it: lower triangle (the factorisation reads nothing else), the identity
+    // on the padding diagonal -- interior (ordered layout) and tail (ba_reset_system_kernel) --, the right-hand side in row N
+    std::vector<double> h((size_t)s_elems), hx((size_t)N);
+    int flow_epoch = 0, used = 0;
+    for (int r = 0; r < num_systems; ++r) {
+        std::fill(h.begin(), h.end(), 0.0);
+        for (int i = 0; i < span; ++i) h[(size_t)i * N + i] = 1.0;      // (every unknown's diagonal is overwritten below)
+        for (int i = span; i < N; ++i) h[(size_t)i * N + i] = 1.0;
+        const double *Ar = A + (size_t)r * n * n, *br = b + (size_t)r * n;
+        for (int u = 0; u < n; ++u) {
+            for (int v = 0; v < n; ++v) {
+                const int pu = pos[u], pv = pos[v];
+                if (pv <= pu) h[(size_t)pu * N + pv] = Ar[(size_t)u * n + v];
+            }
+            h[(size_t)N * N + pos[u]] = br[u];
+        }
+        OSFM_HIP_CHECK(hipMemcpyAsync(S.ptr, h.data(), s_elems * 8, hipMemcpyHostToDevice, s));
+        used = launch_cholesky_solve(S.as<double>(), Lmat.as<double>(), span, Ldiag.as<double>(), xd.as<double>(), infod.as<int>() + r,
+            nullptr, s, form == 0 ? flow_flags.as<int>() : nullptr, ++flow_epoch, form == 0 ? flow_mailbox.as<double>() : nullptr,
+            pattern, max_d, max_groups);
+        OSFM_HIP_CHECK(hipGetLastError());
+        OSFM_HIP_CHECK(hipMemcpyAsync(hx.data(), xd.ptr, (size_t)N * 8, hipMemcpyDeviceToHost, s));
+        OSFM_HIP_CHECK(hipMemcpyAsync(info + r, infod.as<int32_t>() + r, 4, hipMemcpyDeviceToHost, s));
+        OSFM_HIP_CHECK(hipStreamSynchronize(s));            // (h and hx are reused by the next system)
+        for (int u = 0; u < n; ++u) x[(size_t)r * n + u] = hx[pos[u]];
+    }
+    if (launch) {
+        const int32_t v[8] = {used, pl.groups, pl.num_d, pl.num_p, pl.num_tiles, ord.active ? ord.arcs : 0, span, N / 32};
+        memcpy(launch, v, sizeof(v));
+    }
+    return OSFM_OK;
+}
+
 int osfm_ba_options_default(osfm_ba_options *o)
 {
     if (!o) { set_error("ba_options_default: null"); return OSFM_E_ARG; }

@@ -1281,32 +1281,47 @@ void launch_small_solve(const double *A, int n, double *Ldiag, double *x, int *i
     hipLaunchKernelGGL(chol_small_kernel, dim3(1), dim3(128), 0, s, A, NB, n, Ldiag, x, info, d, partials_cam);
 }
 
-// A: (N + 32) x N row-major, rows/cols >= n padded with identity, rhs in row N.
-// Ldiag: N * 32 doubles of scratch for the inverses of the factored diagonal blocks.
-// Returns the form that was launched: 1 the one-launch flow form, 0 launch per block column.
-int launch_cholesky_solve(double *A, double *Lmat, int n, double *Ldiag, double *x, int *info, const LmDev *lm, hipStream_t s,
-    int *flow_flags, int flow_epoch, double *flow_mailbox, FlowPattern pattern)
+// How the one-launch form would run a system of n unknowns (have_flags: flags and a mailbox are there).  The D's sit
+// at the blocks 0, 8, 16, ...; the P workgroups fill the blocks between and behind them.  One P workgroup per tile
+// (rows more than kFlowW below the diagonal, the right-hand side row included) while that fits the device, else the
+// tiles are dealt round robin to as many as do fit.  max_d / max_groups > 0 replace OSFM_FLOW_MAX_D /
+// OSFM_FLOW_MAX_GROUPS (tests: osfm_ba_debug_cholesky_solve).
+FlowPlan chol_flow_plan(int n, bool have_flags, const FlowPattern &pattern, int max_d, int max_groups)
 {
-    static_assert(kFlowBand == kFlowW && kFlowOrderMaxBlocks == kFlowMaxBlocks, "ba_kernels.h mirrors these");
+    FlowPlan pl;
     const int N = cholesky_padded_dim(n);
     const int nblk = N / NB;
-    // The D's sit at the blocks 0, 8, 16, ...; the P workgroups fill the blocks between and behind them.  One P
-    // workgroup per tile (rows more than kFlowW below the diagonal, the right-hand side row included) while that
-    // fits the device, else the tiles are dealt round robin to as many as do fit.
+    pl.nblk = nblk;
     int num_tiles = 0;
     for (int j = 0; j < nblk; ++j) num_tiles += std::max(nblk - kFlowW - j, 0);
     if (pattern.ptiles) num_tiles = pattern.num_ptiles;
     static const int exp_max_d = getenv("OSFM_FLOW_MAX_D") ? atoi(getenv("OSFM_FLOW_MAX_D")) : kFlowMaxD;
     static const int exp_max_groups = getenv("OSFM_FLOW_MAX_GROUPS") ? atoi(getenv("OSFM_FLOW_MAX_GROUPS")) : 1 << 30;
-    const int num_d = std::min(nblk + 1, exp_max_d);
+    const int num_d = std::min(nblk + 1, max_d > 0 ? max_d : exp_max_d);
     const int d_span = 8 * (num_d - 1) + 1;                              // through the last D
     auto d_below = [&](int g) { return std::min((g + 7) >> 3, num_d); };  // D blocks among the first g
     int groups = d_span;
     while (groups - d_below(groups) < num_tiles) ++groups;
-    const int cap = flow_flags && flow_mailbox ? chol_flow_capacity() : 0;
-    groups = std::min(std::min(groups, cap), std::max(exp_max_groups, d_span + 1));
+    const int cap = have_flags ? chol_flow_capacity() : 0;
+    groups = std::min(std::min(groups, cap), std::max(max_groups > 0 ? max_groups : exp_max_groups, d_span + 1));
     const int num_p = groups - d_below(groups);
-    if (flow_flags && flow_mailbox && nblk >= 2 && nblk <= kFlowMaxBlocks && groups >= d_span && (num_tiles == 0 || num_p >= 1)) {
+    pl.groups = groups; pl.num_d = num_d; pl.num_p = num_p; pl.num_tiles = num_tiles; pl.d_span = d_span;
+    pl.flow = have_flags && nblk >= 2 && nblk <= kFlowMaxBlocks && groups >= d_span && (num_tiles == 0 || num_p >= 1);
+    return pl;
+}
+
+// A: (N + 32) x N row-major, rows/cols >= n padded with identity, rhs in row N.
+// Ldiag: N * 32 doubles of scratch for the inverses of the factored diagonal blocks.
+// Returns the form that was launched: 1 the one-launch flow form, 0 launch per block column.
+int launch_cholesky_solve(double *A, double *Lmat, int n, double *Ldiag, double *x, int *info, const LmDev *lm, hipStream_t s,
+    int *flow_flags, int flow_epoch, double *flow_mailbox, FlowPattern pattern, int max_d, int max_groups)
+{
+    static_assert(kFlowBand == kFlowW && kFlowOrderMaxBlocks == kFlowMaxBlocks, "ba_kernels.h mirrors these");
+    const int N = cholesky_padded_dim(n);
+    const int nblk = N / NB;
+    const FlowPlan pl = chol_flow_plan(n, flow_flags && flow_mailbox, pattern, max_d, max_groups);
+    const int groups = pl.groups, num_d = pl.num_d, num_p = pl.num_p, num_tiles = pl.num_tiles;
+    if (pl.flow) {
         CholFlow f;
         f.mailbox = flow_mailbox;
         f.A = A; f.Lmat = Lmat; f.Ldiag = Ldiag; f.flags = flow_flags; f.info = info; f.lm = lm;

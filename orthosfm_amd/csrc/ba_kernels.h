@@ -207,8 +207,14 @@ constexpr int kNzWords = 3;
 constexpr int kFlowBand = 3;
 constexpr int kFlowOrderMaxBlocks = 160;
 struct FlowPattern { const unsigned long long *nz = nullptr; const int32_t *ptiles = nullptr; int num_ptiles = 0; };
+// max_d / max_groups > 0: D workgroups / workgroups of the one-launch form for this call, in place of the process-wide
+// OSFM_FLOW_MAX_D / OSFM_FLOW_MAX_GROUPS (test hook osfm_ba_debug_cholesky_solve)
 int launch_cholesky_solve(double *A, double *Lmat, int n, double *Ldiag, double *x, int *info, const LmDev *lm, hipStream_t s,
-    int *flow_flags = nullptr, int flow_epoch = 0, double *flow_mailbox = nullptr, FlowPattern pattern = FlowPattern());
+    int *flow_flags = nullptr, int flow_epoch = 0, double *flow_mailbox = nullptr, FlowPattern pattern = FlowPattern(),
+    int max_d = 0, int max_groups = 0);
+// the one-launch form's grid for a system of n unknowns, as launch_cholesky_solve sizes it (flow: it would run)
+struct FlowPlan { bool flow = false; int groups = 0, num_d = 0, num_p = 0, num_tiles = 0, d_span = 0, nblk = 0; };
+FlowPlan chol_flow_plan(int n, bool have_flags, const FlowPattern &pattern, int max_d = 0, int max_groups = 0);
 // S[i][i] = 1 for the listed unknowns (interior padding of an ordered layout: identity rows)
 void launch_padding_diagonal(double *S, int ld, const int32_t *pad, int npad, hipStream_t s);
 void chol_flow_set_spin_limit(int limit);   // test hook: polls before a wait gives the launch up (<= 0: default)

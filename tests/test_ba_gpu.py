@@ -508,3 +508,12 @@ def test_ordered_elimination_survives_a_given_up_launch(ba):
     assert s1.flow_fallbacks == 1 and s1.order_arcs > 0
     assert (s1.num_iterations, s1.termination) == (s0.num_iterations, s0.termination)
     assert abs(s1.final_cost - s0.final_cost) <= 1e-10 * s0.final_cost
+
+
+def test_ordered_elimination_meets_the_oracle(ba):
+    """The one-launch Cholesky in the arcs-and-separators layout (ba_order.hip: interior padding rows, zero tiles
+    skipped) against the CPU oracle's dense solve: a 200-camera ring of short tracks, the first case of
+    test_ordered_elimination_of_a_ring_equals_the_natural_order."""
+    sc = synth.make_ba_scene(0, 200, 20000, config_id=81, max_len=12)
+    s, _, _ = _compare_solve(ba, sc)
+    assert s.order_arcs > 0 and s.flow_fallbacks == 0 and s.num_iterations >= 3
