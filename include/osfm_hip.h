@@ -488,6 +488,53 @@ OSFM_API int osfm_ba_options_default(osfm_ba_options *opts);
 OSFM_API int osfm_ba_solve(const osfm_ba_problem *p, const osfm_ba_options *o,
     osfm_ba_summary *s);
 
+/* Test hook: what osfm_ba_solve's kernels computed in its first LM iteration, copied out of the solve itself.
+ * The caller allocates every array; nc = the free camera columns summed over the cameras (their tangent columns in
+ * the cameras' own order: rotation, then offX / offY / scale), M points, C cameras.  Every quantity is in the Jacobi-
+ * scaled tangent space the solve works in.  Copied after the first linearisation (before any factorisation): */
+typedef struct osfm_ba_lin_capture {
+    double *scale_c, *diag_c;     /* [nc] Jacobi scales; LM diagonal: clamped diag(J^T J), unscaled by the radius */
+    double *S;                    /* [nc][nc] reduced camera system, LM term included: lower triangle, zero above */
+    double *rhs;                  /* [nc] its right-hand side Jc^T r - W V^-1 g */
+    double *scale_p, *diag_p;     /* [3M] */
+    double *vinv;                 /* [9M] (V_j + diag_p / radius)^-1 row-major */
+    double *ge;                   /* [3M] Jp^T r summed over the point's observations */
+    /* ... and after the first iteration's solve, camera update, back pass and decision: */
+    double *y_c;                  /* [nc] solution of S y = rhs (the camera step is -y) */
+    double *cand_cams;            /* [7C] candidate cameras */
+    double *cand_points;          /* [4M] candidate points */
+    int32_t nc;                   /* set by the caller: the nc its arrays are sized for (OSFM_E_ARG when the problem's
+                                   * layout has another) */
+    int32_t reserved;
+    /* filled in by the call */
+    double initial_cost, grad_max, radius;       /* after the first linearisation */
+    double model_cost_change, cand_cost;     /* of the first step, as the decision read them */
+    double relative_decrease;     /* (x_cost - cand_cost) / model_cost_change recomputed on the host from the device's
+                                   * values (lm_decide_logic's formula): only `accepted` is the kernel's own decision */
+    int32_t stopped;              /* the solve stopped before its first step (nothing after the first copy is set) */
+    int32_t accepted;             /* the first step was accepted */
+    int32_t flow_aborted;         /* the first factorisation's one-launch form gave its launch up */
+    /* padding rows of the laid-out system (interior ones of an elimination order and the tail up to the block
+     * size): their number, the smallest and largest diagonal entry and the largest |entry| elsewhere in their rows
+     * and columns, right-hand side included */
+    int32_t num_pad;
+    double pad_diag_min, pad_diag_max, pad_off_max;
+    /* the regime the solve took */
+    int32_t win_num, win_over;    /* observation windows; of those, windows of more than 256 observations */
+    int32_t small_lists;          /* pair lists from the scan of a handful of cameras (else the sort) */
+    int32_t dense;                /* dense Schur product (else pair lists) */
+    int32_t dense_splits;         /* its split over K (1: the product written into S in place; 0: no dense product) */
+    int32_t num_pairs, pair_chunk, max_chunks, multi_chunk_pairs;
+    int32_t order_arcs;           /* 0: the cameras' own order */
+    int32_t span, N;              /* laid-out unknowns (padding included), rounded up to the block */
+    int32_t small_solve;          /* N == 32: factorisation and candidate cameras in one launch */
+    int32_t one_launch;           /* the first factorisation took the one-launch form (else launch per column) */
+    int32_t post_fused, back_fused;   /* LM control in the pair / back pass tails (else launches of their own) */
+} osfm_ba_lin_capture;
+/* Runs osfm_ba_solve on p (cam_params / points are updated in place as that does) with the two copies into cap; the
+ * solve's launches and their order are the same.  osfm_ba_solve itself copies nothing. */
+OSFM_API int osfm_ba_debug_linearization(const osfm_ba_problem *p, const osfm_ba_options *o, osfm_ba_lin_capture *cap);
+
 /* Batched ReconstructionAlgorithm::evaluateReprojectionError
  * (OrthoQuaternionRecoAlgorithm.cpp:175-194,
  * OrthographicReconstructionAlgorithm.cpp:204-223): err[k] = ||r_k||_2 in

@@ -311,6 +311,14 @@ static void homog_plus_jacobian(const double *x, double J[4][3])
 
 ORACLE_API void oracle_quat_plus(const double *x, const double *d, double *out) { quat_plus(x, d, out); }
 ORACLE_API void oracle_homog_plus(const double *x, const double *d, double *out) { homog_plus(x, d, out); }
+ORACLE_API void oracle_quat_plus_n(int n, const double *x, const double *d, double *out)
+{
+    for (int i = 0; i < n; ++i) quat_plus(x + 4 * i, d + 3 * i, out + 4 * i);
+}
+ORACLE_API void oracle_homog_plus_n(int n, const double *x, const double *d, double *out)
+{
+    for (int i = 0; i < n; ++i) homog_plus(x + 4 * i, d + 3 * i, out + 4 * i);
+}
 ORACLE_API void oracle_homog_plus_jacobian(const double *x, double *J12) { double J[4][3]; homog_plus_jacobian(x, J); memcpy(J12, J, sizeof J); }
 
 /* ------------------------------------------------------------------ */
@@ -429,6 +437,31 @@ static double evaluate(const ba_problem *p, const ba_options *o, const ba_layout
                 }
         }
     }
+    return cost;
+}
+
+/* What evaluate(..., lin) computes at the problem's own cameras and points, for a reference of one linearisation
+ * built outside (tests/lin_cases.py): per observation the Huber-corrected residual r [O][2] and the tangent Jacobian
+ * blocks Jc [O][2][6] (first cam_ldim columns used, the rest 0) and Jp [O][2][3] (0 when !optimize_points), unscaled;
+ * the cameras' tangent layout cam_off / cam_ldim [C].  Returns the cost. */
+ORACLE_API double
+oracle_ba_linearize(const ba_problem *p, const ba_options *o, double *r, double *Jc, double *Jp, int32_t *cam_off,
+    int32_t *cam_ldim)
+{
+    ba_layout L;
+    layout_build(p, o, &L);
+    const size_t O = (size_t)L.O;
+    ba_lin lin;
+    lin.r = calloc(2 * O + 2, sizeof(double));
+    lin.Jc = calloc(12 * O + 12, sizeof(double));
+    lin.Jp = calloc(6 * O + 6, sizeof(double));
+    const double cost = evaluate(p, o, &L, p->cam_params, p->points, &lin);
+    memcpy(r, lin.r, 2 * O * sizeof(double));
+    memcpy(Jc, lin.Jc, 12 * O * sizeof(double));
+    memcpy(Jp, lin.Jp, 6 * O * sizeof(double));
+    for (int c = 0; c < L.C; ++c) { cam_off[c] = L.cam_off[c]; cam_ldim[c] = L.cam_ldim[c]; }
+    free(lin.r); free(lin.Jc); free(lin.Jp);
+    layout_free(&L);
     return cost;
 }
 

@@ -184,6 +184,39 @@ def debug_cholesky_solve(A, b, cam_ldim=None, pairs=None, form=FORM_AS_SOLVE, ma
     return x, info, dict(zip(_LAUNCH_FIELDS, launch.tolist()))
 
 
+def debug_linearization(problem: FlatProblem, options: capi.BaOptions | None = None, **kw):
+    """osfm_ba_debug_linearization (test hook): osfm_ba_solve on the problem (updated in place as solve() does) with
+    copies of its first LM iteration -- the Jacobi scales, LM diagonals, V^-1 and g of the points, the reduced camera
+    system and rhs in the cameras' own order (lower triangle), then the camera step y_c, the candidate cameras and
+    points and the step's cost figures -- and the regime the solve took.  Returns a dict."""
+    o = options if options is not None else default_options(**kw)
+    C_, M = problem.cam_params.shape[0], problem.points.shape[0]
+    nc = int(_free_columns(problem).sum())
+    shapes = {"scale_c": (nc,), "diag_c": (nc,), "S": (nc, nc), "rhs": (nc,), "scale_p": (M, 3), "diag_p": (M, 3),
+              "vinv": (M, 3, 3), "ge": (M, 3), "y_c": (nc,), "cand_cams": (C_, 7), "cand_points": (M, 4)}
+    out = {k: np.full(max(int(np.prod(v)), 1), np.nan) for k, v in shapes.items()}
+    cap = capi.BaLinCapture()
+    cap.nc = nc                 # (the library refuses a capture sized for another layout)
+    for k in capi.BaLinCapture.ARRAYS:
+        setattr(cap, k, out[k].ctypes.data)
+    st = problem.struct()
+    capi.check(capi.lib.osfm_ba_debug_linearization(C.byref(st), C.byref(o), C.byref(cap)))
+    res = {k: out[k][:int(np.prod(v))].reshape(v) for k, v in shapes.items()}
+    for name, _ in capi.BaLinCapture._fields_:
+        if name not in capi.BaLinCapture.ARRAYS and name not in ("nc", "reserved"):
+            res[name] = getattr(cap, name)
+    return res
+
+
+def _free_columns(problem: FlatProblem) -> np.ndarray:
+    """Free tangent columns per camera (the layout of osfm_ba_solve: rotation as one block of 3 in the quaternion
+    model)."""
+    cc = problem.cam_const
+    if problem.model == 0:
+        return np.where(cc[:, 0] == 0, 3, 0) + (cc[:, 4:7] == 0).sum(axis=1)
+    return (cc[:, :6] == 0).sum(axis=1)
+
+
 def reprojection_errors(problem: FlatProblem, device: int = 0):
     """Batched ReconstructionAlgorithm::evaluateReprojectionError."""
     O = problem.obs_camera.shape[0]

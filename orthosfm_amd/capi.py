@@ -126,10 +126,23 @@ class BaSummary(C.Structure):
                 ("chain_blocks_natural", C.c_int32), ("chain_blocks", C.c_int32)]
 
 
+class BaLinCapture(C.Structure):
+    """osfm_ba_lin_capture (test hook osfm_ba_debug_linearization)."""
+    ARRAYS = ("scale_c", "diag_c", "S", "rhs", "scale_p", "diag_p", "vinv", "ge", "y_c", "cand_cams", "cand_points")
+    _fields_ = [(n, C.c_void_p) for n in ARRAYS] + [("nc", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, C.c_double) for n in ("initial_cost", "grad_max", "radius", "model_cost_change", "cand_cost",
+                                          "relative_decrease")] + \
+               [(n, C.c_int32) for n in ("stopped", "accepted", "flow_aborted", "num_pad")] + \
+               [(n, C.c_double) for n in ("pad_diag_min", "pad_diag_max", "pad_off_max")] + \
+               [(n, C.c_int32) for n in ("win_num", "win_over", "small_lists", "dense", "dense_splits", "num_pairs", "pair_chunk",
+                                         "max_chunks", "multi_chunk_pairs", "order_arcs", "span", "N", "small_solve",
+                                         "one_launch", "post_fused", "back_fused")]
+
+
 # every symbol include/osfm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "osfm_last_error", "osfm_version", "osfm_device_count", "osfm_device_memory", "osfm_library_memory", "osfm_trim_device_memory", "osfm_ransac_selfcheck", "osfm_ba_debug_chol_trace", "osfm_ba_debug_flow_spin_limit", "osfm_ba_debug_order",
-    "osfm_ba_debug_cholesky_solve",
+    "osfm_ba_debug_cholesky_solve", "osfm_ba_debug_linearization",
     "osfm_match_options_default", "osfm_match_create", "osfm_match_create_multi", "osfm_match_get_devices", "osfm_match_destroy",
     "osfm_quantize_sift", "osfm_quantize_surf",
     "osfm_match_set_view", "osfm_match_set_view_float", "osfm_match_view_size", "osfm_match_expect_pairs", "osfm_match_set_positions",

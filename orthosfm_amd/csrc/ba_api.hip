@@ -186,7 +186,8 @@ int finish_device_problem(int model, int C, int M, int O, int nc, double huber, 
 
 namespace { struct SubArray { void *ptr; template <typename T> T *as() const { return static_cast<T *>(ptr); } }; }    // a piece of a DevArray
 
-int ba_solve_core(DeviceProblem &D, const osfm_ba_options &o, StreamLease &sg, int64_t pair_bound, osfm_ba_summary *sum, int *cur_out)
+int ba_solve_core(DeviceProblem &D, const osfm_ba_options &o, StreamLease &sg, int64_t pair_bound, osfm_ba_summary *sum, int *cur_out,
+    osfm_ba_lin_capture *cap)
 {
     const auto t_begin = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
@@ -453,6 +454,92 @@ int ba_solve_core(DeviceProblem &D, const osfm_ba_options &o, StreamLease &sg, i
     OSFM_RETURN_IF(linearize(true, kPostInitial, nullptr));
     OSFM_HIP_CHECK(hipGetLastError());
     lap("first linearize");
+
+    // ---- test hook (osfm_ba_debug_linearization): copies of the first iteration, in the cameras' own order ----
+    std::vector<int32_t> cap_pos;            // the caller's camera unknown u sits at cap_pos[u] of the laid-out system
+    auto capture_linearization = [&]() -> int {
+        std::vector<int32_t> ldim((size_t)C);
+        std::vector<double> hS(s_elems), hdiag((size_t)nc), hscale((size_t)nc);
+        std::vector<PairChunkDesc> desc((size_t)std::max(PL.max_chunks, 1));
+        LmDev st;
+        if (C) OSFM_HIP_CHECK(hipMemcpyAsync(ldim.data(), d.cam_ldim, (size_t)C * 4, hipMemcpyDeviceToHost, s));
+        OSFM_HIP_CHECK(hipMemcpyAsync(hS.data(), S.ptr, s_elems * 8, hipMemcpyDeviceToHost, s));
+        if (nc) {
+            OSFM_HIP_CHECK(hipMemcpyAsync(hdiag.data(), diag_c.ptr, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
+            OSFM_HIP_CHECK(hipMemcpyAsync(hscale.data(), D.scale_c.ptr, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
+        }
+        if (M) {
+            OSFM_HIP_CHECK(hipMemcpyAsync(cap->scale_p, D.scale_p.ptr, (size_t)3 * M * 8, hipMemcpyDeviceToHost, s));
+            OSFM_HIP_CHECK(hipMemcpyAsync(cap->diag_p, diag_p.ptr, (size_t)3 * M * 8, hipMemcpyDeviceToHost, s));
+            OSFM_HIP_CHECK(hipMemcpyAsync(cap->vinv, vinv.ptr, (size_t)9 * M * 8, hipMemcpyDeviceToHost, s));
+            OSFM_HIP_CHECK(hipMemcpyAsync(cap->ge, ge.ptr, (size_t)3 * M * 8, hipMemcpyDeviceToHost, s));
+        }
+        if (num_pairs > 0 && PL.max_chunks > 0)
+            OSFM_HIP_CHECK(hipMemcpyAsync(desc.data(), PL.chunk_desc.ptr, (size_t)PL.max_chunks * sizeof(PairChunkDesc), hipMemcpyDeviceToHost, s));
+        OSFM_HIP_CHECK(hipMemcpyAsync(&st, lm, sizeof(LmDev), hipMemcpyDeviceToHost, s));
+        OSFM_HIP_CHECK(hipStreamSynchronize(s));
+        for (int c = 0, tot = 0; c < C; tot += ldim[c], ++c)
+            for (int i = 0; i < ldim[c]; ++i) cap_pos.push_back((ord.active ? ord.cam_off[c] : tot) + i);
+        const size_t n = cap_pos.size();
+        std::vector<char> taken((size_t)N, 0);
+        for (size_t u = 0; u < n; ++u) {
+            const size_t pu = (size_t)cap_pos[u];
+            taken[pu] = 1;
+            for (size_t v = 0; v < n; ++v) {
+                const size_t pv = (size_t)cap_pos[v];
+                cap->S[u * n + v] = v > u ? 0.0 : hS[std::max(pu, pv) * N + std::min(pu, pv)];
+            }
+            cap->rhs[u] = hS[(size_t)N * N + pu];
+            cap->diag_c[u] = hdiag[pu];
+            cap->scale_c[u] = hscale[pu];
+        }
+        cap->num_pad = 0; cap->pad_diag_min = INFINITY; cap->pad_diag_max = -INFINITY; cap->pad_off_max = 0.0;
+        for (size_t r = 0; r < (size_t)N; ++r) {
+            if (taken[r]) continue;
+            cap->num_pad++;
+            cap->pad_diag_min = std::min(cap->pad_diag_min, hS[r * N + r]);
+            cap->pad_diag_max = std::max(cap->pad_diag_max, hS[r * N + r]);
+            double off = std::fabs(hS[(size_t)N * N + r]);
+            for (size_t q = 0; q < (size_t)N; ++q)
+                if (q != r) off = std::max(off, std::fabs(q < r ? hS[r * N + q] : hS[q * N + r]));
+            cap->pad_off_max = std::max(cap->pad_off_max, off);
+        }
+        cap->initial_cost = st.initial_cost; cap->grad_max = st.grad_max; cap->radius = st.radius;
+        cap->stopped = st.stop;
+        cap->win_num = win.num; cap->win_over = win.num_over;
+        cap->small_lists = PL.small; cap->dense = PL.dense;
+        cap->dense_splits = PL.dense ? schur_dense_splits(d.nc, M) : 0;
+        cap->num_pairs = num_pairs; cap->pair_chunk = PL.chunk; cap->max_chunks = PL.max_chunks;
+        std::vector<char> multi((size_t)std::max(num_pairs, 1), 0);
+        cap->multi_chunk_pairs = 0;
+        if (num_pairs > 0)
+            for (int i = 0; i < PL.max_chunks; ++i)
+                if (desc[i].nchunks > 1 && desc[i].pi >= 0 && desc[i].pi < num_pairs && !multi[desc[i].pi]) { multi[desc[i].pi] = 1; cap->multi_chunk_pairs++; }
+        cap->order_arcs = ord.active ? ord.arcs : 0;
+        cap->span = nc; cap->N = N;
+        cap->small_solve = small;
+        cap->post_fused = post_fused; cap->back_fused = fused;
+        return OSFM_OK;
+    };
+    // behind the first iteration's decision, before the linearisation that follows it overwrites anything
+    auto capture_step = [&](bool one_launch) -> int {
+        std::vector<double> hy((size_t)std::max(nc, 1));
+        LmDev st;
+        if (nc) OSFM_HIP_CHECK(hipMemcpyAsync(hy.data(), y_c.ptr, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
+        // (the first candidate goes to the iterate buffers 1 whatever the decision: buffers 0 are current)
+        if (C) OSFM_HIP_CHECK(hipMemcpyAsync(cap->cand_cams, D.cams[1].ptr, (size_t)7 * C * 8, hipMemcpyDeviceToHost, s));
+        if (M) OSFM_HIP_CHECK(hipMemcpyAsync(cap->cand_points, D.points[1].ptr, (size_t)4 * M * 8, hipMemcpyDeviceToHost, s));
+        OSFM_HIP_CHECK(hipMemcpyAsync(&st, lm, sizeof(LmDev), hipMemcpyDeviceToHost, s));
+        OSFM_HIP_CHECK(hipStreamSynchronize(s));
+        for (size_t u = 0; u < cap_pos.size(); ++u) cap->y_c[u] = hy[cap_pos[u]];
+        cap->model_cost_change = st.model_cost_change; cap->cand_cost = st.cand_cost;
+        cap->relative_decrease = (st.x_cost - (std::isfinite(st.cand_cost) ? st.cand_cost : std::numeric_limits<double>::max())) / st.model_cost_change;
+        cap->accepted = st.cur == 1;
+        cap->flow_aborted = st.flow_aborted;
+        cap->one_launch = one_launch;
+        return OSFM_OK;
+    };
+    if (cap) OSFM_RETURN_IF(capture_linearization());
     const auto t_loop = std::chrono::steady_clock::now();
 
     // Small systems (a handful of cameras: the local adjustments of the incremental
@@ -496,6 +583,7 @@ int ba_solve_core(DeviceProblem &D, const osfm_ba_options &o, StreamLease &sg, i
             // the kernels write the state they leave straight into the host's slot
             launch_lm_decide(lm, prm, sc, eager ? nullptr : &h_state[slot], s);
         }
+        if (cap && it == 0 && !cap->stopped) OSFM_RETURN_IF(capture_step(!small && nc > 0 && !consumed));
         if (!eager) OSFM_HIP_CHECK(hipEventRecord(evs[slot], s));
         OSFM_RETURN_IF(linearize(consumed, kPostLoop, eager ? &h_state[slot] : nullptr));
         OSFM_HIP_CHECK(hipGetLastError());
@@ -733,7 +821,8 @@ int osfm_ba_options_default(osfm_ba_options *o)
     return OSFM_OK;
 }
 
-int osfm_ba_solve(const osfm_ba_problem *p, const osfm_ba_options *opt, osfm_ba_summary *sum)
+// osfm_ba_solve; cap: osfm_ba_debug_linearization's copies (null: none)
+static int ba_solve_host(const osfm_ba_problem *p, const osfm_ba_options *opt, osfm_ba_summary *sum, osfm_ba_lin_capture *cap)
 {
     if (!sum) { set_error("ba_solve: null summary"); return OSFM_E_ARG; }
     memset(sum, 0, sizeof(*sum));
@@ -810,7 +899,7 @@ int osfm_ba_solve(const osfm_ba_problem *p, const osfm_ba_options *opt, osfm_ba_
         bound += pdim ? l * l : l;
     }
     int cur = 0;
-    OSFM_RETURN_IF(ba_solve_core(D, o, sg, bound, sum, &cur));
+    OSFM_RETURN_IF(ba_solve_core(D, o, sg, bound, sum, &cur, cap));
     // ---- write back the current iterate --------------------------------------
     if (C) OSFM_HIP_CHECK(hipMemcpyAsync(p->cam_params, D.cams[cur].ptr, (size_t)7 * C * 8, hipMemcpyDeviceToHost, s));
     if (M) OSFM_HIP_CHECK(hipMemcpyAsync(p->points, D.points[cur].ptr, (size_t)4 * M * 8, hipMemcpyDeviceToHost, s));
@@ -825,6 +914,31 @@ int osfm_ba_solve(const osfm_ba_problem *p, const osfm_ba_options *opt, osfm_ba_
     sum->max_point_change = mx;
     sum->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return OSFM_OK;
+}
+
+int osfm_ba_solve(const osfm_ba_problem *p, const osfm_ba_options *opt, osfm_ba_summary *sum)
+{
+    return ba_solve_host(p, opt, sum, nullptr);
+}
+
+int osfm_ba_debug_linearization(const osfm_ba_problem *p, const osfm_ba_options *opt, osfm_ba_lin_capture *cap)
+{
+    if (!cap) { set_error("ba_debug_linearization: null capture"); return OSFM_E_ARG; }
+    OSFM_RETURN_IF(validate_header(p, "ba_debug_linearization"));
+    // the arrays are the caller's, sized for its nc: the layout's must be the same
+    Layout L;
+    build_camera_layout(p->model, p->num_cameras, p->cam_const, &L);
+    if (cap->nc != L.nc) {
+        set_error("ba_debug_linearization: the capture is sized for %d camera columns, the problem has %d", cap->nc, L.nc);
+        return OSFM_E_ARG;
+    }
+    const bool any_c = p->num_cameras > 0, any_p = p->num_points > 0;
+    if ((any_c && (!cap->scale_c || !cap->diag_c || !cap->S || !cap->rhs || !cap->y_c || !cap->cand_cams)) ||
+        (any_p && (!cap->scale_p || !cap->diag_p || !cap->vinv || !cap->ge || !cap->cand_points))) {
+        set_error("ba_debug_linearization: null capture array"); return OSFM_E_ARG;
+    }
+    osfm_ba_summary sum;
+    return ba_solve_host(p, opt, &sum, cap);
 }
 
 int osfm_ba_reprojection_errors(const osfm_ba_problem *p, int device, double *err, double *residuals)

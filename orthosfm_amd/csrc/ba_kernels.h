@@ -36,6 +36,7 @@ int schur_dense_rows(int nc);            // rows of Zm / Wm (nc rounded up to th
 int schur_dense_cols(int M);             // their leading dimension (3 M rounded up to the K step)
 bool schur_dense_wins(int nc, int M, int64_t entries);      // cost model: the product against `entries` list entries
 size_t schur_dense_partial_bytes(int nc, int M);            // split-K partials (16 when the product is not split)
+int schur_dense_splits(int nc, int M);                      // the product's split over K (1: written into S in place)
 void launch_schur_dense(const BaDev &d, const double *obsrec, const int32_t *obs_lay, double *Zm, double *Wm, double *partial,
     double *S, int ldS, bool first, hipStream_t s);
 
@@ -175,6 +176,7 @@ struct PairListsDev {
     PooledBuffer chunk_start, chunk_pair, chunk_partials, chunk_desc, pair_ticket;
     int num_pairs = 0;
     bool dense = false;          // the lists hold the diagonal pairs only: the rest is ba_dense.hip's product
+    bool small = false;          // built by the scan of a handful of cameras (pair_lists_build_small), not the sort
     int num_entries_all = 0;     // entries of the complete lists (what was counted before the choice)
     int num_entries = 0;
     int max_chunks = 0;

@@ -242,11 +242,13 @@ static int pair_lists_build_small(const BaDev &d, int64_t max_entries, PairLists
 int pair_lists_build(const BaDev &d, bool with_points, int64_t max_entries, PairListsDev *out, hipStream_t s, int dense_policy)
 {
     const int M = d.O;          // the lists are generated per observation
-    out->num_pairs = 0; out->num_entries = 0; out->dense = false; out->num_entries_all = 0;
+    out->num_pairs = 0; out->num_entries = 0; out->dense = false; out->small = false; out->num_entries_all = 0;
     if (M == 0 || d.M == 0) return OSFM_OK;
     const bool no_small = getenv("OSFM_BA_PAIR_LISTS_GENERAL") != nullptr;      // (A/B runs and tests)
-    if (with_points && d.C <= kSmallCams && dense_policy != 1 && !no_small && (int64_t)d.C * (d.C + 1) / 2 * d.M < (1ll << 30))
+    if (with_points && d.C <= kSmallCams && dense_policy != 1 && !no_small && (int64_t)d.C * (d.C + 1) / 2 * d.M < (1ll << 30)) {
+        out->small = true;
         return pair_lists_build_small(d, max_entries, out, s);
+    }
     // per-observation counts, offsets and the hipCUB item counts are 32-bit, and the lists take
     // about 36 bytes per entry up front: long tracks (sum of squared track lengths) are
     // refused here instead of wrapping the offsets

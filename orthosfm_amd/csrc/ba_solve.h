@@ -76,7 +76,9 @@ int finish_device_problem(int model, int C, int M, int O, int nc, double huber, 
 // The Levenberg-Marquardt solve on a finished DeviceProblem (start values in cams[0] / points[0]).  pair_bound: an
 // upper bound of the Schur pair entries (sum of squared track lengths), refused beyond 2^31 - 1.  On return
 // *cur names the buffer pair (cams[cur], points[cur]) that holds the result; the stream is synchronised.
-int ba_solve_core(DeviceProblem &D, const osfm_ba_options &o, StreamLease &sg, int64_t pair_bound, osfm_ba_summary *sum, int *cur);
+// cap (test hook osfm_ba_debug_linearization; null in every solve): the first iteration's quantities are copied out
+int ba_solve_core(DeviceProblem &D, const osfm_ba_options &o, StreamLease &sg, int64_t pair_bound, osfm_ba_summary *sum, int *cur,
+    osfm_ba_lin_capture *cap = nullptr);
 
 int select_device(int device);
 

@@ -370,6 +370,37 @@ def oracle_ba_jacobian(scene, k):
     return r, jc, jp
 
 
+def oracle_ba_linearize(scene, **opt_kw):
+    """What the oracle's evaluate() gives one linearisation at the scene's cameras and points (unscaled, from its
+    jets): Huber-corrected residuals r (O, 2), tangent Jacobians Jc (O, 2, 6) -- the first cam_ldim columns of the
+    observation's camera -- and Jp (O, 2, 3), the cameras' tangent layout cam_off / cam_ldim (C,), and the cost."""
+    lib = oracle()
+    p = ba_problem_struct(scene)
+    o = ba_default_options(**opt_kw)
+    O, Cn = scene.obs_camera.shape[0], scene.cam_params.shape[0]
+    r, jc, jp = np.zeros((O, 2)), np.zeros((O, 2, 6)), np.zeros((O, 2, 3))
+    off, ldim = np.zeros(max(Cn, 1), dtype=np.int32), np.zeros(max(Cn, 1), dtype=np.int32)
+    lib.oracle_ba_linearize.argtypes = [C.POINTER(OBaProblem), C.POINTER(OBaOptions), _f64p, _f64p, _f64p, _i32p, _i32p]
+    lib.oracle_ba_linearize.restype = C.c_double
+    cost = lib.oracle_ba_linearize(C.byref(p), C.byref(o), r.reshape(-1), jc.reshape(-1), jp.reshape(-1), off, ldim)
+    return {"r": r, "Jc": jc, "Jp": jp, "cam_off": off[:Cn].astype(np.int64), "cam_ldim": ldim[:Cn].astype(np.int64),
+            "cost": cost}
+
+
+def oracle_plus(kind, x, d):
+    """The oracle's local parameterisation Plus of n blocks at once: kind "quat" (EigenQuaternionParameterization,
+    x (n, 4) stored x, y, z, w) or "homog" (HomogeneousVectorParameterization(4)); d (n, 3)."""
+    lib = oracle()
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 4)
+    d = np.ascontiguousarray(d, dtype=np.float64).reshape(-1, 3)
+    out = np.empty_like(x)
+    fn = lib.oracle_quat_plus_n if kind == "quat" else lib.oracle_homog_plus_n
+    fn.argtypes = [C.c_int, _f64p, _f64p, _f64p]
+    fn.restype = None
+    fn(x.shape[0], x.reshape(-1), d.reshape(-1), out.reshape(-1))
+    return out
+
+
 def oracle_ba_triangulate(scene):
     lib = oracle()
     p = ba_problem_struct(scene)
