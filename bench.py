@@ -19,14 +19,20 @@ of a shared page-locked host segment and only the per-pair counts are all-gather
 RCCL -- `--exchange rccl` gathers the lists themselves over xGMI instead, as a
 multi-node run would.
 
-Reported beside it on rank 0 at N = 1 (each with the CPU path timed on the host cores):
-the same pass through RANSAC-F, a variant whose gates reject pairs and matches, the
-cascade-hashing mode, track building, the per-pair latency of the drop-in interface,
-the global bundle adjustment of configs[3] with its roofline, the 200-image matching
-run on one GPU, and the end-to-end job (match -> tracks -> groups -> incremental
-bundle adjustment) on the 200-image set.
+A plain run does what the headline needs and nothing more: it sets up, warms up, times the
+steps, writes --dump-outputs and prints the line (with the tile kernel's roofline, read from
+the timed steps themselves).  With `--full`, reported beside it on rank 0 at N = 1 (each
+with the CPU path timed on the host cores, the lists of the timed pass compared with the
+CPU oracle's): the same pass through RANSAC-F, a variant whose gates reject pairs and
+matches, the cascade-hashing mode, special SIFT rows and FEATURE_ALL, track building, the
+per-pair latency of the drop-in interface, the global bundle adjustment of configs[3] with
+its roofline, the 200-image matching run on one GPU, and the end-to-end job (match ->
+tracks -> groups -> incremental bundle adjustment) on the 200-image set; at N > 1, the
+CPU baseline, the pass through RANSAC-F, track building over the exchanged lists and the
+bundle adjustment.  The --no-* options leave legs out of a --full run.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
 
 `--dump-outputs DIR` writes what the last timed step returned (records and match lists of
 rank 0's pairs, see dump_outputs) so that two builds can be compared output for output: the
@@ -73,7 +79,7 @@ HBM_PEAK_GBS = 8000.0
 METRIC = "image-pairs matched/sec + BA iterations/sec (N images, M tracks) at 1/2/4/8 GPU"
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -100,11 +106,22 @@ def parse():
                     help="how the match lists reach rank 0 for N > 1: shared host segment (one node) or RCCL gather")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned (rank 0's pairs) as DIR/<name>.npy, at most 64 MB")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (CPU baselines and the parity checks "
+                         "against them, the passes with RANSAC-F, gates at work, cascade hashing, special SIFT rows "
+                         "and FEATURE_ALL, track building, the drop-in latency, the bundle adjustments with their "
+                         "roofline, the 200-image run and the end-to-end job; at N > 1 track building over the "
+                         "exchanged lists) and allow --config 1; the --no-* options leave legs out of it")
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.config == 1 and not args.full:
+        ap.error("--config 1 is a measurement beside the headline: it needs --full")
     if args.dump_outputs and args.config == 1:
         ap.error("--dump-outputs belongs to the matching pass, not to the --config 1 plumbing run")
+    if not args.full:
+        # a plain run is the headline alone: set up, warm up, the timed steps, --dump-outputs and the line
+        args.no_cpu_baseline = args.no_ba = args.no_verify = args.no_e2e = args.no_realistic = True
     return args
 
 
@@ -1107,7 +1124,7 @@ def main():
 
     # N > 1: rank 0 consumes the lists of all ranks where the exchange left them
     exchanged = None
-    if rank == 0 and world > 1 and gathered[0] is not None:
+    if args.full and rank == 0 and world > 1 and gathered[0] is not None:
         exchanged = exchanged_tracks(gathered[0], all_pairs, V, F, args.exchange)
 
     tracks = None

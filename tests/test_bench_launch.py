@@ -65,13 +65,14 @@ import pytest  # noqa: E402
 @pytest.mark.gpu
 def test_two_ranks_from_a_plain_launch_on_one_gpu():
     """VERDICT r4 #2 "Done": the driver's own command form with --gpus 2 (gloo: two ranks share the
-    one device of the box) prints ONE line with n_gpus = 2 and the lists of both ranks exchanged."""
+    one device of the box) prints ONE line with n_gpus = 2 and the lists of both ranks exchanged
+    (--full: the parity check and the track building over the exchanged lists are not headline)."""
     import json
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--no-ba", "--no-e2e",
-                        "--no-verify", "--views", "12", "--features", "3000", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--full", "--no-ba",
+                        "--no-e2e", "--no-verify", "--views", "12", "--features", "3000", "--steps", "2", "--warmup", "1",
                         "--cpu-sample-pairs", "2"],
                        env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
