@@ -1,7 +1,9 @@
 // The bundle-adjustment solve on device-resident arrays: what osfm_ba_solve (host arrays in, host arrays out)
-// and the device-resident scene (scene_api.hip: the arrays never leave the device) both run.
+// and the device-resident scene (scene_api.hip: the arrays never leave the device) both run.  The problem is built
+// by ba_api.hip / scene_api.hip, solved by ba_solve.hip.
 #pragma once
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <utility>
 #include <vector>
@@ -57,28 +59,77 @@ struct ReducedOrder {
 // (out->active == false, chain_natural filled in): the natural order stands.
 bool choose_reduced_order(int C, const int32_t *ldim, const std::vector<std::pair<int, int>> &pairs, ReducedOrder *out);
 
+// The problem as the triangulation, reprojection and LM kernels read it: the caller's arrays, the camera layout, and
+// the second iterate buffers.  The solve only reads it; its scales, camera tables and LM state are its own.
 struct DeviceProblem {
     DevArray cams[2], points[2], obs_xy, obs_cam, obs_pt, pt_start, img_w, img_h;
-    DevArray cam_ldim, cam_off, colmap, scale_c, scale_p;
-    DevArray camder[2];       // the cameras' derived table rows, per iterate buffer (ba_solve_core)
+    DevArray cam_ldim, cam_off, colmap;
     BaDev dev;
 };
 
 // which columns of a camera block are free (SetupParameterBlocks, OrthoQuaternionRecoAlgorithm.cpp:121-148,
 // OrthographicReconstructionAlgorithm.cpp:148-178), from the constancy masks [C][7]
 void build_camera_layout(int model, int C, const uint8_t *cam_const, Layout *L);
-// D->cam_ldim / cam_off / colmap / scale_c from L (L outlives the queued copies: the caller's concern)
-int upload_camera_layout(const Layout &L, int C, hipStream_t s, DeviceProblem *D);
 // D->dev from the arrays D holds (cams[0], points[0], obs_*, pt_start, img_*, the camera layout); allocates the
-// candidate buffers, the point scales and the per-observation point index
+// candidate buffers and the per-observation point index
 int finish_device_problem(int model, int C, int M, int O, int nc, double huber, int pdim, hipStream_t s, DeviceProblem *D);
 
-// The Levenberg-Marquardt solve on a finished DeviceProblem (start values in cams[0] / points[0]).  pair_bound: an
-// upper bound of the Schur pair entries (sum of squared track lengths), refused beyond 2^31 - 1.  On return
-// *cur names the buffer pair (cams[cur], points[cur]) that holds the result; the stream is synchronised.
-// cap (test hook osfm_ba_debug_linearization; null in every solve): the first iteration's quantities are copied out
-int ba_solve_core(DeviceProblem &D, const osfm_ba_options &o, StreamLease &sg, int64_t pair_bound, osfm_ba_summary *sum, int *cur,
-    osfm_ba_lin_capture *cap = nullptr);
+// The Levenberg-Marquardt solve (ba_solve.hip) on a finished DeviceProblem (start values in cams[0] / points[0]), which it
+// leaves as it was.  pair_bound: an upper bound of the Schur pair entries (sum of squared track lengths), refused beyond
+// 2^31 - 1.  On return *cur names the buffer pair (cams[cur], points[cur]) that holds the result; the stream is
+// synchronised.  cap (test hook osfm_ba_debug_linearization; null in every solve): copies of the first iteration
+int ba_solve_core(const DeviceProblem &D, const osfm_ba_options &o, StreamLease &sg, int64_t pair_bound, osfm_ba_summary *sum,
+    int *cur, osfm_ba_lin_capture *cap = nullptr);
+
+// The dense Cholesky's buffers for a system of span unknowns, padded to N: S with the right-hand side in row N, the
+// factor, Ldiag, the solution y; for the one-launch form (flow) its hand-off flags, zeroed here once, and mailbox
+struct CholeskyBuffers {
+    DevArray S, L, Ldiag, y, flags, mailbox;
+    int N = 0, epoch = 0;             // epoch: differs from every earlier solve on the same flags
+    size_t s_elems = 0;               // of S and L: (N + 32) x N
+    bool flow = false;
+    int alloc(int span, bool allow_flow, hipStream_t s)
+    {
+        const int n = std::max(span, 1);
+        N = cholesky_padded_dim(n);
+        s_elems = (size_t)(N + 32) * N;
+        OSFM_RETURN_IF(S.alloc(s_elems * 8));
+        OSFM_RETURN_IF(L.alloc(s_elems * 8));
+        OSFM_RETURN_IF(Ldiag.alloc((size_t)N * 32 * 8));
+        OSFM_RETURN_IF(y.alloc((size_t)N * 8));
+        flow = allow_flow && N > 32;          // (a system of one block never takes the one-launch form: chol_small_kernel)
+        if (flow) {
+            OSFM_RETURN_IF(flags.alloc((size_t)chol_flow_flag_count(n) * 4));
+            OSFM_HIP_CHECK(hipMemsetAsync(flags.ptr, 0, (size_t)chol_flow_flag_count(n) * 4, s));
+            OSFM_RETURN_IF(mailbox.alloc(chol_flow_mailbox_bytes(n)));
+        }
+        return OSFM_OK;
+    }
+    // S (lower triangle) -> y; one_launch: the one-launch form where flow.  Returns 1 when that form ran
+    int solve(int span, int *info, const LmDev *lm, bool one_launch, const FlowPattern &pattern, hipStream_t s, int max_d = 0, int max_groups = 0)
+    {
+        return launch_cholesky_solve(S.as<double>(), L.as<double>(), span, Ldiag.as<double>(), y.as<double>(), info, lm, s,
+            one_launch ? flags.as<int>() : nullptr, ++epoch, one_launch ? mailbox.as<double>() : nullptr, pattern, max_d, max_groups);
+    }
+};
+
+// where the caller's camera unknowns (ldim[c] per camera) sit in the laid-out system; cam_off (may be null): each camera's first
+inline std::vector<int32_t> unknown_positions(int C, const int32_t *ldim, const ReducedOrder &ord, int32_t *cam_off = nullptr)
+{
+    std::vector<int32_t> pos;
+    for (int c = 0, tot = 0; c < C; tot += ldim[c], ++c) {
+        const int off = ord.active ? ord.cam_off[c] : tot;
+        if (cam_off) cam_off[c] = off;
+        for (int i = 0; i < ldim[c]; ++i) pos.push_back(off + i);
+    }
+    return pos;
+}
+
+using Clock = std::chrono::steady_clock;
+inline void lap(int verbose, Clock::time_point t0, const char *what)       // verbose >= 2: the time since t0 on stderr
+{
+    if (verbose >= 2) fprintf(stderr, "[osfm ba] %-18s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+}
 
 int select_device(int device);
 

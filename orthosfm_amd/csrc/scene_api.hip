@@ -359,8 +359,6 @@ int build_problem(osfm_scene *sc, const int32_t *sel, const int32_t *scan, int O
     }
     memcpy(reinterpret_cast<int8_t *>(pack.data() + 4 * Cz), L->colmap.data(), (size_t)6 * C);
     OSFM_RETURN_IF(upload(out->cam_block, pack.data(), pack.size(), s));
-    OSFM_RETURN_IF(D.scale_c.alloc((size_t)L->nc * 8));
-    launch_fill(D.scale_c.as<double>(), (size_t)L->nc, 1.0, s);
     OSFM_RETURN_IF(finish_device_problem(sc->model, C, M, O, L->nc, huber, pdim, s, &D));
     const int32_t *blk = out->cam_block.as<int32_t>();
     D.dev.img_w = blk; D.dev.img_h = blk + Cz; D.dev.cam_ldim = blk + 2 * Cz; D.dev.cam_off = blk + 3 * Cz;
