@@ -122,6 +122,7 @@ struct osfm_matcher {
     // scratch (grow-only)
     DeviceBuffer d_problems[2], rowparts, colparts, out, keep, mark_off[2], counts[2];
     DeviceBuffer exact_items, exact_count, stage_in, flags;
+    DeviceBuffer rs_count, rs_items;      // bucketed rescoring of the SIFT finish: bucket fill counts, items
     DeviceBuffer sp_parts, sp_col, d_spjobs;      // match_special_kernel: row results, column results, job list
     DeviceBuffer clock_probe;
     DeviceBuffer zero_tile;               // kTileCols blank descriptors: filler tiles of the correction-free tile loop
@@ -252,6 +253,7 @@ int run_batch(osfm_matcher *m, const osfm_pair *pairs, int num_pairs, const Batc
     bool any_c0[2] = {false, false}, any_corrected[2] = {false, false};
     int64_t macs = 0, alg_bytes = 0, macs_surf = 0;
     int64_t cas_queries[2] = {0, 0};
+    int64_t rs_buckets = 0, rs_items = 0;     // bucketed rescoring (SIFT problems of the tile path)
 
     // Segment length of the correction-free problems: a workgroup walks seg_cols columns for its 256 rows.
     // Every segment costs a prologue (A fragments, two tiles), a row merge and a set of row partials, so a
@@ -370,6 +372,12 @@ int run_batch(osfm_matcher *m, const osfm_pair *pairs, int num_pairs, const Batc
             pr.nseg = empty ? 0 : (pr.n2 + pr.seg_cols - 1) / pr.seg_cols;
             pr.n2stride = round_up(pr.n2, kCycleCols);
             pr.block_start = total_blocks[type];
+            pr.rs_bucket_off = rs_buckets;
+            pr.rs_item_off = rs_items;
+            if (type == 0 && !cascade && !empty) {
+                rs_buckets += rescore_buckets(pr.nrb_main, pr.n2);
+                rs_items += rescore_items(pr.nrb_main, pr.n2);
+            }
             if (cascade) {
                 // no score tiles: the candidate search works on the hash data of the two views
                 const ViewData *vd[2] = {&a, &b};
@@ -427,6 +435,14 @@ int run_batch(osfm_matcher *m, const osfm_pair *pairs, int num_pairs, const Batc
     OSFM_RETURN_IF(m->keep.reserve(grown(std::max<int64_t>(keep_bytes, 16))));
     OSFM_RETURN_IF(m->exact_items.reserve(grown(total_queries) * sizeof(ExactItem)));
     OSFM_RETURN_IF(m->exact_count.reserve(16));
+    // OSFM_FINISH_RESCAN=wave: every refinement of the finish through its per-query rescan (read per batch)
+    const char *rescan_env = getenv("OSFM_FINISH_RESCAN");
+    const bool bucketed = rs_buckets > 0 && rs_buckets <= INT_MAX && max_n[0] < (1 << 26) &&
+                          !(rescan_env && strcmp(rescan_env, "wave") == 0);
+    if (bucketed) {
+        OSFM_RETURN_IF(m->rs_count.reserve(grown(rs_buckets) * sizeof(int32_t)));
+        OSFM_RETURN_IF(m->rs_items.reserve(grown(rs_items) * sizeof(RescoreItem)));
+    }
     OSFM_RETURN_IF(m->sp_parts.reserve((size_t)std::max<int64_t>(sp_recs, 1) * sizeof(RowPart)));
     hipStream_t s = m->stream;
     {
@@ -535,9 +551,15 @@ int run_batch(osfm_matcher *m, const osfm_pair *pairs, int num_pairs, const Batc
                     m->sp_parts.as<RowPart>(), m->sp_col.as<int32_t>(), s);
                 OSFM_HIP_CHECK(hipEventRecord(m->ev_sp[1], s));
             }
+            const bool rs = type == 0 && bucketed;
+            if (rs) OSFM_HIP_CHECK(hipMemsetAsync(m->rs_count.ptr, 0, (size_t)rs_buckets * sizeof(int32_t), s));
             launch_match_finish(dp, np, max_n[type], m->rowparts.as<RowPart>(),
                 m->colparts.as<ColPart>(), m->sp_parts.as<RowPart>(), m->sp_col.as<int32_t>(), tab, 0,
-                m->exact_items.as<ExactItem>(), ecount, ecap, s);
+                m->exact_items.as<ExactItem>(), ecount, ecap, rs ? m->rs_count.as<int32_t>() : nullptr,
+                rs ? m->rs_items.as<RescoreItem>() : nullptr, s);
+            if (rs)
+                launch_match_rescore(dp, np, m->rs_count.as<int32_t>(), m->rs_items.as<RescoreItem>(), rs_buckets, tab,
+                    m->exact_items.as<ExactItem>(), ecount, ecap, s);
             launch_exact_scan(type == 0 ? 128 : 64, dp, m->exact_items.as<ExactItem>(), ecount, ecap,
                 tab, s);
         }

@@ -78,6 +78,10 @@ struct MatchProblem {
     const int32_t *cas_start[2];
     const int32_t *cas_items[2];
     int64_t cas_state_off[2];        // first query of direction 0 / 1 in the candidate-key scratch
+    // bucketed rescoring of the SIFT finish (match_rescore_kernel): this problem's first bucket and first
+    // item slot (its buckets: nrb_main * 4 of direction 1, then 32 * rescore_windows(n2) of direction 0)
+    int64_t rs_bucket_off;
+    int64_t rs_item_off;
 };
 
 struct RowPart { int32_t ip_best, idx_best, ip_second, pad; };
@@ -129,10 +133,36 @@ void launch_match_tiles(int ch, bool masked, bool any_special, bool any_c0, bool
     unsigned long long *clock_probe = nullptr,       // [2]: shader cycles / 100 MHz ticks, added up by sampled workgroups of the C0 kernel
     const int8_t *zero_tile = nullptr);              // kTileCols blank descriptors (the correction-free kernel's filler tiles)
 
+// Bucketed rescoring of the winning groups (SIFT).  A query that passes the finish kernel's
+// optimistic test has its winning group of 32 candidates rescored exactly; for the groups of the
+// raw tile kernels that happens by bucket instead of per query:
+//   direction 1 (column queries): bucket = (problem, row block, 64-row strip): the strip holds the
+//     32-row groups of both half-waves (ColPart code = 2 * strip + half);
+//   direction 0 (row queries, RowPart.pad == 1): bucket = (problem, lane slot lr = idx & 31, window
+//     of kRescoreWin starting tiles): every group that starts in the window draws from the 64
+//     columns 64 t + 32 h + lr of the window's kRescoreWin + 15 tiles.
+// Either way a bucket has 64 candidates, read once and scored against all its queries on the
+// matrix cores.  A bucket holds up to kRescoreCap1 / kRescoreCap0 queries; the finish kernel keeps
+// the rest (and everything else it refines) on its own per-query rescan.
+constexpr int kRescoreWin = 17;                 // 2 * (17 + 15) = 64 candidate columns
+constexpr int kRescoreCap0 = 32, kRescoreCap1 = 64;
+struct RescoreItem { int32_t q_sub; int32_t ip2; };    // q_sub = query * 32 + (half-wave | tile in window)
+__host__ __device__ inline int rescore_windows(int n2) { return ((n2 + kTileCols - 1) / kTileCols + kRescoreWin - 1) / kRescoreWin; }
+__host__ __device__ inline int rescore_buckets(int nrb_main, int n2) { return nrb_main * 4 + 32 * rescore_windows(n2); }
+__host__ __device__ inline int64_t rescore_items(int nrb_main, int n2)
+{
+    return (int64_t)nrb_main * 4 * kRescoreCap1 + (int64_t)32 * rescore_windows(n2) * kRescoreCap0;
+}
+
+// rs_count / rs_items null: every refinement takes the per-query rescan (SURF, and OSFM_FINISH_RESCAN=wave)
 void launch_match_finish(const MatchProblem *d_problems, int num_problems,
     int max_n, const RowPart *rowparts, const ColPart *colparts, const RowPart *sp_parts, const int32_t *sp_col, LoweTable tab,
     int force_exact, ExactItem *exact_items, int32_t *exact_count, int exact_cap,
-    hipStream_t s);
+    int32_t *rs_count, RescoreItem *rs_items, hipStream_t s);
+// rescores the buckets [0, total_buckets) the finish kernel filled (SIFT only); before launch_exact_scan
+void launch_match_rescore(const MatchProblem *d_problems, int num_problems, const int32_t *rs_count,
+    const RescoreItem *rs_items, int64_t total_buckets, LoweTable tab, ExactItem *exact_items, int32_t *exact_count,
+    int exact_cap, hipStream_t s);
 
 void launch_exact_scan(int dim, const MatchProblem *d_problems,
     const ExactItem *items, const int32_t *count, int exact_cap, LoweTable tab,

@@ -897,7 +897,7 @@ __global__ __launch_bounds__(128) void
 match_finish_kernel(const MatchProblem *__restrict__ problems, const RowPart *__restrict__ rowparts,
     const ColPart *__restrict__ colparts, const RowPart *__restrict__ sp_parts, const int32_t *__restrict__ sp_col,
     LoweTable tab, int force_exact, ExactItem *__restrict__ exact_items, int32_t *__restrict__ exact_count, int exact_cap,
-    int blocks_per_dir, int total_blocks)
+    int32_t *__restrict__ rs_count, RescoreItem *__restrict__ rs_items, int blocks_per_dir, int total_blocks)
 {
     // every XCD works through a contiguous run of problems, so the descriptors the
     // rescans gather from are fetched into one L2 instead of all eight
@@ -1034,6 +1034,36 @@ match_finish_kernel(const MatchProblem *__restrict__ problems, const RowPart *__
     } else {
         sp_scan = false;
     }
+    // The groups of the raw tile kernels go to the bucketed rescoring (match_rescore_kernel, which
+    // writes the result) while their bucket has room; everything else is rescanned here.
+    bool deferred = false;
+    if (!SIGNED && DIM == 128 && rs_count != nullptr && refine) {
+        int b = -1, sub = 0, cap = 0;
+        int64_t item = 0;
+        const int nb1 = pd.nrb_main * 4;
+        if (dir == 1) {
+            if (kind1 == 0 && idx1 < pd.nrb_main && code < 8) {
+                b = idx1 * 4 + (code >> 1); sub = code & 1;
+                item = (int64_t)b * kRescoreCap1; cap = kRescoreCap1;
+            }
+        } else if (kind1 == 1) {
+            const int tq = idx1 >> 6;        // the group's first tile
+            if (tq < (pd.n2 + kTileCols - 1) / kTileCols) {
+                const int w = tq / kRescoreWin, k = w * 32 + (idx1 & 31);
+                b = nb1 + k; sub = tq - w * kRescoreWin;
+                item = (int64_t)nb1 * kRescoreCap1 + (int64_t)k * kRescoreCap0; cap = kRescoreCap0;
+            }
+        }
+        if (b >= 0) {
+            const int slot = atomicAdd(rs_count + pd.rs_bucket_off + b, 1);
+            if (slot < cap) {
+                RescoreItem it;
+                it.q_sub = q * 32 + sub; it.ip2 = ip2;
+                rs_items[pd.rs_item_off + item + slot] = it;
+                refine = false; deferred = true;
+            }
+        }
+    }
     // Queries that pass get their best group re-scored, one query at a time by
     // the whole wave.  The rescan also yields the exact best of the group: it
     // differs from ip1 only when ip1 = 0 came from a padding column (raw path),
@@ -1093,12 +1123,12 @@ match_finish_kernel(const MatchProblem *__restrict__ problems, const RowPart *__
             exact_items[slot] = it;
         }
     }
-    if (active) out[q] = res;
+    if (active && !deferred) out[q] = res;
 }
 
 void launch_match_finish(const MatchProblem *d_problems, int num_problems, int max_n,
     const RowPart *rowparts, const ColPart *colparts, const RowPart *sp_parts, const int32_t *sp_col, LoweTable tab, int force_exact,
-    ExactItem *exact_items, int32_t *exact_count, int exact_cap, hipStream_t s)
+    ExactItem *exact_items, int32_t *exact_count, int exact_cap, int32_t *rs_count, RescoreItem *rs_items, hipStream_t s)
 {
     if (num_problems <= 0 || max_n <= 0) return;
     const int blocks_per_dir = (max_n + 127) / 128;
@@ -1107,10 +1137,193 @@ void launch_match_finish(const MatchProblem *d_problems, int num_problems, int m
     const dim3 grid((unsigned)total);
     if (tab.is_signed)
         hipLaunchKernelGGL((match_finish_kernel<64, true>), grid, dim3(128), 0, s, d_problems, rowparts,
-            colparts, sp_parts, sp_col, tab, force_exact, exact_items, exact_count, exact_cap, blocks_per_dir, (int)total);
+            colparts, sp_parts, sp_col, tab, force_exact, exact_items, exact_count, exact_cap, nullptr, nullptr,
+            blocks_per_dir, (int)total);
     else
         hipLaunchKernelGGL((match_finish_kernel<128, false>), grid, dim3(128), 0, s, d_problems, rowparts,
-            colparts, sp_parts, sp_col, tab, force_exact, exact_items, exact_count, exact_cap, blocks_per_dir, (int)total);
+            colparts, sp_parts, sp_col, tab, force_exact, exact_items, exact_count, exact_cap, rs_count, rs_items,
+            blocks_per_dir, (int)total);
+}
+
+// ---------------------------------------------------------------------------
+// Bucketed rescoring (see match_kernels.h): one wave per bucket, kRescorePerWave consecutive buckets
+// per wave.  The bucket's 64 candidates are the A operand of two 32 x 32 i8 MFMA blocks, held in
+// registers for all its queries (read once per bucket instead of once per query); 32 queries at a
+// time are the B operand.  Lane l then holds query l & 31 against 16 candidates of each block
+// (rows (r & 3) + 8 (r >> 2) + 4 (l >> 5) of the C layout); per query it keeps exactly what
+// rescan_groups returns: keys score * 32 + n over the query's own 32 candidates, n the position in
+// rescan order, the same masks, the same tail.
+// ---------------------------------------------------------------------------
+constexpr int kRescorePerWave = 16;
+static_assert(2 * (kRescoreWin + 15) <= 64, "a direction-0 bucket's candidates fill two MFMA blocks at most");
+
+// (four waves per SIMD: the kernel is a chain of dependent loads per bucket, what hides it is waves)
+__global__ __launch_bounds__(256, 4) void
+match_rescore_kernel(const MatchProblem *__restrict__ problems, int num_problems, const int32_t *__restrict__ rs_count,
+    const RescoreItem *__restrict__ rs_items, int total_buckets, int total_blocks, LoweTable tab,
+    ExactItem *__restrict__ exact_items, int32_t *__restrict__ exact_count, int exact_cap)
+{
+    __shared__ __attribute__((aligned(16))) int corr_s[4][64];
+    // consecutive workgroups (one problem's buckets) on one XCD: its descriptors are fetched into one L2
+    const int lin = xcd_remap(blockIdx.x, total_blocks);
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
+    const int b0 = (lin * 4 + wv) * kRescorePerWave;
+    if (b0 >= total_buckets) return;
+    const int cnt_l = lane < kRescorePerWave && b0 + lane < total_buckets ? rs_count[b0 + lane] : 0;
+    unsigned long long todo = __ballot(cnt_l > 0);
+    if (!todo) return;
+    // the problem of the first live bucket (largest p with rs_bucket_off <= b); later ones by stepping
+    int p = 0;
+    {
+        const int b = b0 + __ffsll((long long)todo) - 1;
+        int lo = 0, hi = num_problems - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (problems[mid].rs_bucket_off <= b) lo = mid; else hi = mid - 1;
+        }
+        p = lo;
+    }
+    const v16i zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    while (todo) {
+        const int k = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const int b = b0 + k;
+        while (p + 1 < num_problems && problems[p + 1].rs_bucket_off <= b) ++p;
+        const MatchProblem &pd = problems[p];
+        const int local = b - (int)pd.rs_bucket_off;
+        const int nb1 = pd.nrb_main * 4;
+        const int dir = local < nb1 ? 1 : 0;
+        // candidate of slot o (0..63), -1 for none -- the masks of rescan_groups
+        //   dir 1: row  strip + o                      (strip = first row of the 64-row strip)
+        //   dir 0: column 64 (w0 + o / 2) + 32 (o & 1) + lr   (w0 = first tile of the window)
+        int strip = 0, w0 = 0, lr = 0, cap;
+        int64_t item0;
+        if (dir == 1) {
+            strip = (local >> 2) * kRowsPerBlock + (local & 3) * 64;
+            cap = kRescoreCap1;
+            item0 = pd.rs_item_off + (int64_t)local * kRescoreCap1;
+        } else {
+            const int l0 = local - nb1;
+            w0 = (l0 >> 5) * kRescoreWin; lr = l0 & 31;
+            cap = kRescoreCap0;
+            item0 = pd.rs_item_off + (int64_t)nb1 * kRescoreCap1 + (int64_t)l0 * kRescoreCap0;
+        }
+        auto cand_of = [&](int o) {
+            if (dir == 1) { const int r = strip + o; return r < pd.n1 ? r : -1; }
+            const int c = kTileCols * (w0 + (o >> 1)) + 32 * (o & 1) + lr;
+            return c < pd.n2 ? c : -1;
+        };
+        const int cnt = min(__builtin_amdgcn_readlane(cnt_l, k), cap);
+        const int8_t *Cm = dir == 0 ? pd.B : pd.A;
+        const int8_t *Qm = dir == 0 ? pd.A : pd.B;
+        const int32_t *corrC = dir == 0 ? pd.corrB : pd.corrA;
+        const int32_t *corrQ = dir == 0 ? pd.corrA : pd.corrB;
+        int32_t *out = dir == 0 ? pd.m12 : pd.m21;
+        // the first block's items before the candidates: the query loads that depend on them are then
+        // one memory latency behind, not two
+        RescoreItem it0;
+        it0.q_sub = 0; it0.ip2 = 0;
+        if (j < cnt) it0 = rs_items[item0 + j];
+        // the candidates: slot 32 bk + j of lane half h holds bytes (2 ks + h) * 16 .. +16 in k-step ks
+        // (the tile kernel's operand order; the B operand below uses the same one)
+        v4i a[2][4];
+#pragma unroll
+        for (int bk = 0; bk < 2; ++bk) {
+            const int cs = max(cand_of(32 * bk + j), 0);       // no candidate: row 0, masked below
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+                a[bk][ks] = *reinterpret_cast<const v4i *>(Cm + (size_t)cs * 128 + (ks * 2 + h) * 16);
+        }
+        {
+            const int c = cand_of(lane);
+            // INT_MIN marks a slot without candidate (corrections stay far from it)
+            corr_s[wv][lane] = c >= 0 ? corrC[c] : INT_MIN;
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (int qb = 0; qb < cnt; qb += 32) {
+            const bool live = qb + j < cnt;
+            RescoreItem it = it0;
+            if (qb > 0) {
+                it.q_sub = 0; it.ip2 = 0;
+                if (live) it = rs_items[item0 + qb + j];
+            }
+            const int q = it.q_sub >> 5, sub = it.q_sub & 31;
+            v4i bq[4];
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+                bq[ks] = *reinterpret_cast<const v4i *>(Qm + (size_t)q * 128 + (ks * 2 + h) * 16);
+            const int cq = corrQ[q];
+            v16i acc[2];
+#pragma unroll
+            for (int bk = 0; bk < 2; ++bk) {
+                acc[bk] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[bk][0], bq[0], zero16, 0, 0, 0);
+#pragma unroll
+                for (int ks = 1; ks < 4; ++ks)
+                    acc[bk] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[bk][ks], bq[ks], acc[bk], 0, 0, 0);
+            }
+            // keys of the query's own candidates: distinct, so (best, second) is a max / med3 pair
+            int kbest = INT_MIN, ksec = INT_MIN;
+#pragma unroll
+            for (int bk = 0; bk < 2; ++bk)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int ob = 32 * bk + 8 * g + 4 * h;           // slots ob .. ob + 3
+                    const v4i cc = *reinterpret_cast<const v4i *>(&corr_s[wv][ob]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int o = ob + e;
+                        int n;
+                        bool ok;
+                        if (dir == 1) {
+                            // o = 32 (n >> 4) + (r & 3) + 8 (r >> 2) + 4 half, r = n & 15
+                            n = 16 * bk + 4 * g + e;
+                            ok = h == sub;
+                        } else {
+                            // o = 2 (tile - first tile of the group) + column half
+                            n = o - 2 * sub;
+                            ok = (unsigned)n < 32u;
+                        }
+                        const int key = ok && cc[e] != INT_MIN ? (acc[bk][4 * g + e] + cq + cc[e]) * 32 + n : INT_MIN;
+                        ksec = med3a(kbest, ksec, key);
+                        kbest = max(kbest, key);
+                    }
+                }
+            // the other lane half holds the query's other candidates
+            const int obest = __shfl_xor(kbest, 32), osec = __shfl_xor(ksec, 32);
+            const int wbest = max(kbest, obest);
+            const int wsec = max(min(kbest, obest), max(ksec, osec));
+            if (live && h == 0) {
+                const int pos = wbest & 31;
+                const int o = dir == 1 ? 32 * (pos >> 4) + (pos & 3) + 8 * ((pos >> 2) & 3) + 4 * sub : pos + 2 * sub;
+                const int idx = max(cand_of(o), 0);
+                const int rbest = wbest >> 5;
+                const int rsecond = max(wsec == INT_MIN ? INT_MIN : wsec >> 5, it.ip2);
+                const int res = accept_match(rbest, rsecond, idx, tab);
+                out[q] = res;
+                // accepted although two candidates tie for best: the sequential scan decides
+                if (res >= 0 && rsecond == rbest) {
+                    const int slot = atomicAdd(exact_count, 1);
+                    if (slot < exact_cap) {
+                        ExactItem e;
+                        e.problem = p; e.dir = dir; e.query = q;
+                        exact_items[slot] = e;
+                    }
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();    // corr_s is rewritten by the next bucket
+    }
+}
+
+void launch_match_rescore(const MatchProblem *d_problems, int num_problems, const int32_t *rs_count,
+    const RescoreItem *rs_items, int64_t total_buckets, LoweTable tab, ExactItem *exact_items, int32_t *exact_count,
+    int exact_cap, hipStream_t s)
+{
+    if (num_problems <= 0 || total_buckets <= 0) return;
+    const int64_t blocks = (total_buckets + 4 * kRescorePerWave - 1) / (4 * kRescorePerWave);
+    if (total_buckets > INT_MAX || blocks > INT_MAX) return;    // the caller keeps such batches on the per-query rescan
+    hipLaunchKernelGGL(match_rescore_kernel, dim3((unsigned)blocks), dim3(256), 0, s, d_problems, num_problems,
+        rs_count, rs_items, (int)total_buckets, (int)blocks, tab, exact_items, exact_count, exact_cap);
 }
 
 // ---------------------------------------------------------------------------
