@@ -392,7 +392,7 @@ int run_batch(osfm_matcher *m, const osfm_pair *pairs, int num_pairs, const Batc
                 total_blocks[type] += pr.nrb * pr.nseg;
                 pr.rowpart_off = rowpart_recs;
                 rowpart_recs += (int64_t)pr.nseg * pr.nrb * kRowsPerBlock;
-                pr.colpart_off = colpart_recs;
+                pr.colpart_off = colpart_recs;                 // nrb * n2stride records = two int32 planes of that many entries
                 colpart_recs += (int64_t)pr.nrb * pr.n2stride;
             }
             // placed by offset into m->out after allocation (store offsets now)

@@ -24,7 +24,8 @@ struct MatchProblem {
     int32_t seg_cols;       // columns per segment: kSegCols, or up to kSegColsMax for correction-free problems
     int32_t block_start;    // first workgroup of this problem in the launch
     int64_t rowpart_off;    // into RowPart[]: [nseg][nrb*256]
-    int64_t colpart_off;    // into ColPart[]: [nrb][n2stride]
+    int64_t colpart_off;    // into ColPart[], in ColPart units; the problem's nrb * n2stride records are laid out as two
+                            // int32 planes of [nrb][n2stride]: the best keys, then the second keys
     int32_t *m12;           // [n1] result (set 1 -> set 2), device
     int32_t *m21;           // [n2]
     int32_t out_off12;      // combine_results offset added to valid m12 entries
@@ -85,6 +86,8 @@ struct MatchProblem {
 };
 
 struct RowPart { int32_t ip_best, idx_best, ip_second, pad; };
+// One column partial: the unit of the partials' sizing and offsets and the form they have in LDS.  In global memory
+// a problem's best keys and second keys lie in separate planes (MatchProblem::colpart_off).
 struct ColPart { int32_t key_best, key_second; };
 
 // Bijective XCD-aware remap (device code only): consecutive logical blocks (which share the

@@ -106,13 +106,28 @@ template <int V> struct IntC { static constexpr int value = V; };
 // A column partial is written once and read once, by the finish kernel, after 5 GB of its kind: stored non-temporally
 // it does not push the column bank of the pair out of the XCD's L2 on its way (the 64 workgroups an XCD runs side by
 // side all stream the same 2.5 MB of descriptors).
-__device__ __forceinline__ void store_colpart(ColPart *dst, const ColPart &v)
+// In global memory a problem's partials are two int32 planes of [nrb][n2stride] entries, the best keys and right
+// behind them the second keys (the finish kernel streams the first and gathers one entry per column from the other).
+// `best` / `second`: uniform addresses (scalar registers), `byte_off`: the lane's 32-bit offset -- the stores take
+// the scalar-base form, no 64-bit lane pointer is built or held.
+__device__ __forceinline__ void store_colpart(int32_t *best, int32_t *second, unsigned byte_off, const ColPart &v)
 {
+    int32_t *const pb = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(best) + byte_off);
+    int32_t *const ps = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(second) + byte_off);
 #ifdef OSFM_COLPART_PLAIN_STORE
-    *dst = v;
+    *pb = v.key_best; *ps = v.key_second;
 #else
-    __builtin_nontemporal_store(*reinterpret_cast<const unsigned long long *>(&v), reinterpret_cast<unsigned long long *>(dst));
+    __builtin_nontemporal_store(v.key_best, pb);
+    __builtin_nontemporal_store(v.key_second, ps);
 #endif
+}
+// The same for the correction-free kernel's tile loop, where the compiler, given a base that changes from store to
+// store, adds it to a 64-bit lane pointer with vector instructions and holds the pointers of both planes in vector
+// registers.  Like that loop's DMA (stage_tile) the stores are invisible to the compiler; dma_wait() counts them.
+__device__ __forceinline__ void store_colpart_sbase(int32_t *best, int32_t *second, unsigned byte_off, const ColPart &v)
+{
+    asm volatile("global_store_dword %0, %1, %2 nt" :: "v"(byte_off), "v"(v.key_best), "s"(best) : "memory");
+    asm volatile("global_store_dword %0, %1, %2 nt" :: "v"(byte_off), "v"(v.key_second), "s"(second) : "memory");
 }
 
 // RAW = true: row operand in raw form (see MatchProblem): the accumulator IS
@@ -159,7 +174,9 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
     const int n1 = pd.n1, n2 = pd.n2, n2stride = pd.n2stride;
     const int8_t *const Bbase = C0 ? pd.B_raw : pd.B;
     const int32_t *const corrBbase = pd.corrB;
-    ColPart *const colout = colparts + pd.colpart_off + (int64_t)rb * pd.n2stride;
+    // this row block's rows of the two column-partial planes (see store_colpart)
+    int32_t *const colbest = reinterpret_cast<int32_t *>(colparts + pd.colpart_off) + (int64_t)rb * pd.n2stride;
+    int32_t *const colsecond = colbest + (int64_t)pd.nrb * pd.n2stride;
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63, lr = lane & 31, lh = lane >> 5;
     const int row0 = rb * kRowsPerBlock + wave * 64;      // row slot (partials, validity)
@@ -223,6 +240,9 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
     // as a scalar: the DMA then addresses with a scalar base + vector offset and a
     // scalar LDS destination, no vector arithmetic per tile
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    // the lane's byte offset inside a tile's 64 entries of a column-partial plane, held in a register like lane_off
+    unsigned lane4 = (unsigned)lane * 4u;
+    if (PIPE) asm volatile("" : "+v"(lane4));
     unsigned lane_off[CPT];
 #pragma unroll
     for (int c = 0; c < CPT; ++c) {
@@ -233,11 +253,13 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
     }
     // (vector-memory operations complete in issue order: behind a tile whose phase stored a merged column partial --
     //  issued after the tile's two DMA pieces -- waiting for all but the youngest is waiting for the pieces; the
-    //  store's acknowledgement is not something the next tile needs)
+    //  store's acknowledgement is not something the next tile needs.  A merged partial is two stores, one per plane:
+    //  all but the two youngest.  A smaller count would wait for a store at every fourth tile, a larger one would
+    //  let a tile be read before it has landed.)
     auto dma_wait = [&](bool store_behind = false) {
         if (!PIPE) return;
 #ifndef OSFM_TILE_WAIT_ALL
-        if (store_behind) { asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); return; }
+        if (store_behind) { asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); return; }
 #endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
@@ -305,8 +327,9 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
     // third on; everything is straight-line code (a branch would split the block).
     // RS >= 0 -- slot RS of THIS fragment was closed by the phase before:
     // its running best restarts from this tile's scores (no reset needed there).
+    // (tms: tm as a scalar, for the addresses of the stores)
     auto phase = [&](auto ph_c, auto cl_c, auto mg_c, auto rs_c, v16i (&cur)[2], v16i (&nxt)[2], int buf_next,
-                     int tile0, int tm) {
+                     int tile0, int tm, int tms) {
         constexpr int PH = decltype(ph_c)::value;
         constexpr int CL = decltype(cl_c)::value;
         constexpr int RS = decltype(rs_c)::value;
@@ -390,7 +413,7 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
                     }
                     cpm[0].key_best = k1; cpm[0].key_second = k2;
                 } else {
-                    store_colpart(colout + col_begin + tm * kTileCols + lane, cpm[0]);
+                    store_colpart_sbase(colbest + col_begin + tms * kTileCols, colsecond + col_begin + tms * kTileCols, lane4, cpm[0]);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -485,7 +508,7 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
             ColPart out;
             out.key_best = k1;
             out.key_second = k2;
-            store_colpart(colout + col, out);
+            store_colpart(colbest, colsecond, (unsigned)col * 4u, out);
         }
     };
 
@@ -513,8 +536,8 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
             const int tm = max(tt - 5, 0) + wave;
             // restarts: the fragment 0 slot closed by phase (u-1, 1), the fragment 1 slot by phase (u, 0)
             phase(IntC<0>(), IntC<u>(), IntC<(u & 3) == 1 ? 1 : 0>(), IntC<(u + 15) & 15>(), acc0, acc1, bn,
-                max(tt - 16, 0), tm);
-            phase(IntC<1>(), IntC<u>(), IntC<0>(), IntC<u>(), acc1, acc0, bn, max(tt - 15, 0), 0);
+                max(tt - 16, 0), tm, max(tt - 5, 0) + wave_s);
+            phase(IntC<1>(), IntC<u>(), IntC<0>(), IntC<u>(), acc1, acc0, bn, max(tt - 15, 0), 0, 0);
             tile_bottom(tt, (u & 3) == 1);       // phase (u, 0) of these tiles stores a merged partial
         };
         // (whole cycles only: blank tiles fill the last one, see stage_tile -- a tail of single tiles costs 2.5x
@@ -538,8 +561,8 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
     if (!PIPE)
     for (; t < ntiles; ++t) {
         tile_top(t);
-        phase(IntC<0>(), IntC<-1>(), IntC<0>(), IntC<-1>(), acc0, acc1, (t & 1) ^ 1, 0, 0);   // reduce (rf 0, t), produce (rf 1, t), fetch B(t+1)
-        phase(IntC<1>(), IntC<-1>(), IntC<0>(), IntC<-1>(), acc1, acc0, (t & 1) ^ 1, 0, 0);   // reduce (rf 1, t), produce (rf 0, t+1)
+        phase(IntC<0>(), IntC<-1>(), IntC<0>(), IntC<-1>(), acc0, acc1, (t & 1) ^ 1, 0, 0, 0);   // reduce (rf 0, t), produce (rf 1, t), fetch B(t+1)
+        phase(IntC<1>(), IntC<-1>(), IntC<0>(), IntC<-1>(), acc1, acc0, (t & 1) ^ 1, 0, 0, 0);   // reduce (rf 1, t), produce (rf 0, t+1)
         if (PIPE ? t == ntiles - 1 : ((t % kGroupTiles) == kGroupTiles - 1 || t == ntiles - 1)) {
             const int first = PIPE ? t_tail : (t / kGroupTiles) * kGroupTiles;
             close_all([&](int, int) { return first; });
@@ -892,6 +915,11 @@ scan_specials(const MatchProblem &pd, int dir, int q, int lane, int &best_out, i
     idx_out = map[wbest & 511];
 }
 
+// Row blocks per batch of the column merge's loads (measured: 8 costs 0.2 ms per 1225-pair step against 16).
+#ifndef OSFM_FINISH_BATCH
+#define OSFM_FINISH_BATCH 16
+#endif
+
 template <int DIM, bool SIGNED>
 __global__ __launch_bounds__(128) void
 match_finish_kernel(const MatchProblem *__restrict__ problems, const RowPart *__restrict__ rowparts,
@@ -973,34 +1001,39 @@ match_finish_kernel(const MatchProblem *__restrict__ problems, const RowPart *__
                 }
             }
         } else {
-            // eight row blocks per round, their loads issued together (left as a plain
-            // loop the compiler emits load, wait, fold per row block: one memory latency
-            // per partial with a single request in flight per lane)
-            constexpr int kBatch = 8;
-            const ColPart *cp0 = colparts + pd.colpart_off + q;
+            // The column partials are two planes (store_colpart); only the best keys are streamed.  Sixteen row
+            // blocks per round, their loads issued together (left as a plain loop the compiler emits load, wait,
+            // fold per row block: one memory latency per partial with a single request in flight per lane).
+            // Why the second keys of all row blocks but the winning one are not needed: the merged second is
+            // max(second of the winner, best of every other block) -- a block's second key is never above its
+            // best key, and the fold takes in the best of every block that does not win in the end: on arrival
+            // if it loses there (min(ip1, pb) = pb), and when it is overtaken if it led for a while (pb >= ip1,
+            // so min(ip1, pb) = the displaced ip1).  Both bound that block's second from above.
+            constexpr int kBatch = OSFM_FINISH_BATCH;
+            const int32_t *best0 = reinterpret_cast<const int32_t *>(colparts + pd.colpart_off) + q;
             const int nrb = pd.nrb;
             const int64_t stride = pd.n2stride;
             for (int rb0 = 0; rb0 < nrb; rb0 += kBatch) {
-                ColPart p[kBatch];
+                int kb[kBatch];
 #pragma unroll
                 for (int u = 0; u < kBatch; ++u)
-                {
-                    // (read once, 5 GB of them per launch: non-temporal, so that they do not push the descriptors the
-                    //  rescans gather out of the L2)
-                    const unsigned long long raw = __builtin_nontemporal_load(
-                        reinterpret_cast<const unsigned long long *>(cp0 + (int64_t)min(rb0 + u, nrb - 1) * stride));     // clamped repeats are not folded
-                    p[u].key_best = (int)(raw & 0xffffffffu); p[u].key_second = (int)(raw >> 32);
-                }
+                    // (read once, 2.5 GB of them per launch: non-temporal, so that they do not push the descriptors
+                    //  the rescans gather out of the L2)
+                    kb[u] = __builtin_nontemporal_load(best0 + (int64_t)min(rb0 + u, nrb - 1) * stride);     // clamped repeats are not folded
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < kBatch; ++u) {
                     // no branch (a branch would let the optimiser sink each load to its use)
                     const bool live = rb0 + u < nrb;
-                    const int pb = (!live || p[u].key_best == kKeyNone) ? INT_MIN : (p[u].key_best >> 8);
-                    const int ps = (!live || p[u].key_second == kKeyNone) ? INT_MIN : (p[u].key_second >> 8);
-                    ip2 = max(max(ip2, ps), min(ip1, pb));
-                    if (pb >= ip1 && pb != INT_MIN) { ip1 = pb; idx1 = rb0 + u; code = p[u].key_best & 255; }
+                    const int pb = (!live || kb[u] == kKeyNone) ? INT_MIN : (kb[u] >> 8);
+                    ip2 = max(ip2, min(ip1, pb));
+                    if (pb >= ip1 && pb != INT_MIN) { ip1 = pb; idx1 = rb0 + u; code = kb[u] & 255; }      // later block wins ties
                 }
+            }
+            // the winner's second key: one gathered entry of the second plane, right behind the best plane
+            if (ip1 != INT_MIN) {
+                const int ks = __builtin_nontemporal_load(best0 + ((int64_t)nrb + idx1) * stride);
+                ip2 = max(ip2, ks == kKeyNone ? INT_MIN : (ks >> 8));
             }
         }
         if (pd.sp && (dir == 0 ? pd.nsB : pd.nsA) > 0) {
