@@ -323,7 +323,8 @@ typedef struct osfm_match_stats {
     int64_t algorithmic_bytes;   /* descriptors read once + results written */
     double lowres_kernel_ms;     /* same, launches of the low-res gate (limited variant) */
     int32_t lowres_kernel_launches;
-    int32_t reserved;
+    int32_t tile_workgroups;     /* workgroups of the full-matching tile launches: row blocks x column segments
+                                  * (like every field here: of the most recent call, which starts from zero) */
     int64_t lowres_mac_count;
     double cashash_kernel_ms;    /* cascade hashing mode: candidate search + NN kernel */
     int32_t cashash_kernel_launches;

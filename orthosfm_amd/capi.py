@@ -68,7 +68,7 @@ class MatchStats(C.Structure):
     _fields_ = [("tile_kernel_ms", C.c_double), ("tile_kernel_launches", C.c_int32),
                 ("exact_scan_queries", C.c_int32), ("mac_count", C.c_int64),
                 ("algorithmic_bytes", C.c_int64), ("lowres_kernel_ms", C.c_double),
-                ("lowres_kernel_launches", C.c_int32), ("reserved", C.c_int32),
+                ("lowres_kernel_launches", C.c_int32), ("tile_workgroups", C.c_int32),
                 ("lowres_mac_count", C.c_int64), ("cashash_kernel_ms", C.c_double),
                 ("cashash_kernel_launches", C.c_int32), ("special_kernel_launches", C.c_int32),
                 ("special_kernel_ms", C.c_double), ("tile_shader_cycles", C.c_double), ("tile_refclk_ticks", C.c_double),

@@ -125,7 +125,7 @@ struct osfm_matcher {
     DeviceBuffer rs_count, rs_items;      // bucketed rescoring of the SIFT finish: bucket fill counts, items
     DeviceBuffer sp_parts, sp_col, d_spjobs;      // match_special_kernel: row results, column results, job list
     DeviceBuffer clock_probe;
-    DeviceBuffer zero_tile;               // kTileCols blank descriptors: filler tiles of the correction-free tile loop
+    DeviceBuffer zero_tile;               // kTileCols blank descriptors: what the correction-free tile loop prefetches past a segment's end
     int special_max = 512;                // views with more special descriptors take the per-view operand forms
     int expect_pairs = 0;                 // osfm_match_expect_pairs: the largest call to come (work arrays sized for it)
     DeviceBuffer d_m12_off, d_len12, d_corr_off, d_keep_pair, d_corr;
@@ -605,6 +605,7 @@ int run_batch(osfm_matcher *m, const osfm_pair *pairs, int num_pairs, const Batc
         } else {
             m->stats.tile_kernel_ms += ms;
             m->stats.tile_kernel_launches += 1;
+            m->stats.tile_workgroups += total_blocks[type];
             if (type == 1) { m->stats.surf_tile_kernel_ms += ms; m->stats.surf_tile_kernel_launches += 1; }
         }
     }
@@ -1897,7 +1898,7 @@ int osfm_match_get_stats(const osfm_matcher *m, osfm_match_stats *out)
             out->special_kernel_launches += t.special_kernel_launches; out->special_kernel_ms += t.special_kernel_ms;
             out->tile_shader_cycles += t.tile_shader_cycles; out->tile_refclk_ticks += t.tile_refclk_ticks;
             out->surf_tile_kernel_ms += t.surf_tile_kernel_ms; out->surf_tile_kernel_launches += t.surf_tile_kernel_launches;
-            out->surf_mac_count += t.surf_mac_count;
+            out->surf_mac_count += t.surf_mac_count; out->tile_workgroups += t.tile_workgroups;
         }
         return OSFM_OK;
     }

@@ -134,7 +134,7 @@ void launch_match_tiles(int ch, bool masked, bool any_special, bool any_c0, bool
     const MatchProblem *d_problems,
     int num_problems, int total_blocks, RowPart *rowparts, ColPart *colparts, hipStream_t s,
     unsigned long long *clock_probe = nullptr,       // [2]: shader cycles / 100 MHz ticks, added up by sampled workgroups of the C0 kernel
-    const int8_t *zero_tile = nullptr);              // kTileCols blank descriptors (the correction-free kernel's filler tiles)
+    const int8_t *zero_tile = nullptr);              // kTileCols blank descriptors (the correction-free kernel's prefetches past a segment's end)
 
 // Bucketed rescoring of the winning groups (SIFT).  A query that passes the finish kernel's
 // optimistic test has its winning group of 32 candidates rescored exactly; for the groups of the

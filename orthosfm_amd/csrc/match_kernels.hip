@@ -239,7 +239,10 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
     // per-lane byte offset inside a tile (loop invariant, 32 bits) and the wave id
     // as a scalar: the DMA then addresses with a scalar base + vector offset and a
     // scalar LDS destination, no vector arithmetic per tile
-    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    // (opaque: the tile loop has a block per tile, and the register allocator would re-read the lane register at
+    //  every use instead of keeping the scalar -- a vector instruction or two per tile)
+    if (PIPE) asm volatile("" : "+s"(wave_s));
     // the lane's byte offset inside a tile's 64 entries of a column-partial plane, held in a register like lane_off
     unsigned lane4 = (unsigned)lane * 4u;
     if (PIPE) asm volatile("" : "+v"(lane4));
@@ -263,12 +266,15 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
 #endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
-    auto stage_tile = [&](int t, int buf) {
+    auto tile_src = [&](int t) {
         const int8_t *src = Bbase + (size_t)(col_begin + t * kTileCols) * D;      // uniform
-        // PIPE: the tile loop runs whole cycles; the tiles behind the segment's last one are blank
-        // (zero descriptors score 0 against everything, which changes nothing: the reference's
-        // running state starts at (0, 0) and the correction-free products are >= 0)
+        // PIPE: the tile loop prefetches two tiles ahead and leaves behind the segment's last tile; the
+        // prefetches that run past the end read blanks (never consumed by an epilogue: the MFMAs of the
+        // first one are issued, their result is dead)
         if (PIPE && t >= ntiles) src = zero_tile;
+        return src;
+    };
+    auto stage_tile_at = [&](const int8_t *src, int t, int buf) {
 #pragma unroll
         for (int c = 0; c < CPT; ++c) {
             const int q0 = (c * 4 + wave_s) * 64;         // first chunk of this wave-instruction
@@ -297,6 +303,10 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
                 (glb_void *)(corrBbase + col_begin + t * kTileCols + lane),
                 (lds_void *)(uintptr_t)(corrbuf + buf * 64), 4, 0, 0);
     };
+    auto stage_tile = [&](int t, int buf) { stage_tile_at(tile_src(t), t, buf); };
+    // PIPE: the source of the next tile to stage, worked out one tile ahead -- the tile loop has a block per tile,
+    // and scalar work at the head of a block stands between the barrier and the DMA it feeds
+    const int8_t *pf_src = nullptr;
 
     // B fragments (and column corrections) of one 32-column group, LDS -> registers
     v4i b[2][KS];
@@ -328,9 +338,11 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
     // RS >= 0 -- slot RS of THIS fragment was closed by the phase before:
     // its running best restarts from this tile's scores (no reset needed there).
     // (tms: tm as a scalar, for the addresses of the stores)
-    auto phase = [&](auto ph_c, auto cl_c, auto mg_c, auto rs_c, v16i (&cur)[2], v16i (&nxt)[2], int buf_next,
+    // PRE -- the first MFMA of the phase was issued by the tile before, in front of its barrier (first_mfma).
+    auto phase = [&](auto ph_c, auto cl_c, auto mg_c, auto rs_c, auto pre_c, v16i (&cur)[2], v16i (&nxt)[2], int buf_next,
                      int tile0, int tm, int tms) {
         constexpr int PH = decltype(ph_c)::value;
+        constexpr bool PRE = decltype(pre_c)::value != 0;
         constexpr int CL = decltype(cl_c)::value;
         constexpr int RS = decltype(rs_c)::value;
         constexpr bool MG = decltype(mg_c)::value != 0;
@@ -345,7 +357,9 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
 #pragma unroll
         for (int i = 0; i < NCHUNK; ++i) {
             const int cf = i / KS, ks = i % KS;
-            if (ks == 0)
+            if (PRE && i == 0)
+                ;       // issued by first_mfma(): the same operands as the ks == 0 line below -- change both together
+            else if (ks == 0)
                 nxt[cf] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[PH ^ 1][0], b[cf][0], C0 ? zero16 : ra[PH ^ 1], 0, 0, 0);
             else
                 nxt[cf] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[PH ^ 1][ks], b[cf][ks], nxt[cf], 0, 0, 0);
@@ -398,7 +412,11 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
                 const int r = CL;
                 const int gk = (int)(((unsigned)rcur[OF][r] << kRawShift) | (unsigned)tile0);
                 rsecbuf[(OF * 16 + r) * 256 + tid] = med3a(rbest[OF][r], sv, gk);
-                rbest[OF][r] = max(rbest[OF][r], gk);
+                int nb = max(rbest[OF][r], gk);
+                // pinned here: with the cycle's exits the optimiser would otherwise sink the update to the
+                // cycle's end and the exit edges, keeping the group key of every slot alive until there
+                if (PIPE) asm volatile("" : "+v"(nb));
+                rbest[OF][r] = nb;
                 // no reset: the next phase that touches this slot restarts it (RS)
             }
             if (MG && (i == 2 || i == 3)) {
@@ -420,6 +438,15 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
         }
     };
 
+    // The first MFMA of a tile's phase 0 (row fragment 1 x column group 0 of the fragments fetched during the tile
+    // before; its accumulator was reduced by that tile's phase 1).  With the tile loop in one block the compiler
+    // moved it in front of the barrier at the foot of the tile before, where the matrix pipe works while the wave
+    // waits; the exits of the cycle end the block at every barrier, so it is issued there by hand.
+    auto first_mfma = [&]() {
+        acc1[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[1][0], b[0][0], C0 ? zero16 : ra[1], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
     // --- prologue: tiles 0 and 1 into LDS, fragments of tile 0, first half of tile 0
     stage_tile(0, 0);
     stage_tile(PIPE || ntiles > 1 ? 1 : 0, 1);
@@ -434,13 +461,24 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
         for (int ks = 1; ks < KS; ++ks)
             acc0[cf] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[0][ks], b[cf][ks], acc0[cf], 0, 0, 0);
     }
+    if (PIPE) {
+        first_mfma();
+        pf_src = tile_src(2);
+        asm volatile("" : "+s"(pf_src));
+    }
     __syncthreads();        // every wave holds tile 0 in registers: its LDS buffer may be refilled
 
     // per-tile steps shared by the two loop forms below
     auto tile_top = [&](int t) {
         // tile t+2 into the buffer tile t was read from (clamped: the extra
         // refills of the last tile are never consumed)
-        stage_tile(PIPE ? t + 2 : min(t + 2, ntiles - 1), t & 1);
+        if (PIPE) {
+            stage_tile_at(pf_src, t + 2, t & 1);
+            pf_src = tile_src(t + 3);
+            asm volatile("" : "+s"(pf_src));
+        } else {
+            stage_tile(min(t + 2, ntiles - 1), t & 1);
+        }
 #pragma unroll
         for (int cf = 0; cf < 2; ++cf) {
             if (!RAW) {
@@ -457,7 +495,7 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
     // half-waves of a column are exchanged with one v_permlane32_swap so that
     // lane == column within the tile, then the wave's (best, second) goes to LDS.
     // group code = wave * 2 + half-wave (32 rows: both fragments of the half-wave)
-    auto tile_bottom = [&](int t, bool store_behind = false) {
+    auto tile_bottom = [&](int t, bool store_behind = false, bool pre_issue = false) {
         int kk[2];
 #pragma unroll
         for (int cf = 0; cf < 2; ++cf) {
@@ -470,6 +508,7 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
         cp.key_best = max(x0, x1);
         cp.key_second = min(x0, x1);
         colbuf[((t & 7) * 4 + wave) * 64 + lane] = cp;
+        if (pre_issue) first_mfma();
         dma_wait(store_behind);
         __syncthreads();
     };
@@ -528,41 +567,92 @@ tile_body(const MatchProblem &pd, int rb, int seg, RowPart *__restrict__ rowpart
         // In the first cycle the closes of not yet started groups fold "nothing"
         // into (best, second): a no-op.
         static_assert(kPipeGroupTiles == 16, "the staggered schedule closes one of 16 slots per phase");
+        // The cycle is left behind its last real tile (tile_bottom has drained the DMA and passed the
+        // workgroup barrier; ntiles is the same in all four waves: a uniform, scalar branch between two
+        // tiles, none inside a phase).  true: that was the segment's last tile.
         auto cycle_tile = [&](auto u_c, int t0) {
             constexpr int u = decltype(u_c)::value;
             const int tt = t0 + u;
             tile_top(tt);
             const int bn = (tt & 1) ^ 1;
-            const int tm = max(tt - 5, 0) + wave;
+            const int tm0 = u >= 5 ? tt - 5 : max(tt - 5, 0);     // first tile of the batch a (u & 3) == 1 tile merges
+            const int tm = tm0 + wave;
             // restarts: the fragment 0 slot closed by phase (u-1, 1), the fragment 1 slot by phase (u, 0)
-            phase(IntC<0>(), IntC<u>(), IntC<(u & 3) == 1 ? 1 : 0>(), IntC<(u + 15) & 15>(), acc0, acc1, bn,
-                max(tt - 16, 0), tm, max(tt - 5, 0) + wave_s);
-            phase(IntC<1>(), IntC<u>(), IntC<0>(), IntC<u>(), acc1, acc0, bn, max(tt - 15, 0), 0, 0);
-            tile_bottom(tt, (u & 3) == 1);       // phase (u, 0) of these tiles stores a merged partial
+            phase(IntC<0>(), IntC<u>(), IntC<(u & 3) == 1 ? 1 : 0>(), IntC<(u + 15) & 15>(), IntC<1>(), acc0, acc1, bn,
+                max(tt - 16, 0), tm, tm0 + wave_s);
+            phase(IntC<1>(), IntC<u>(), IntC<0>(), IntC<u>(), IntC<0>(), acc1, acc0, bn, max(tt - 15, 0), 0, 0);
+            tile_bottom(tt, (u & 3) == 1, true);     // phase (u, 0) of these tiles stores a merged partial
+            return tt + 1 >= ntiles;
         };
-        // (whole cycles only: blank tiles fill the last one, see stage_tile -- a tail of single tiles costs 2.5x
-        //  the vector instructions per tile and a close of all slots)
-        const int tcyc = (ntiles + 15) & ~15;
-        for (; t < tcyc; t += 16) {
+        // Whole cycles while more tiles follow them: one block, no exit.  The last 1 .. 16 tiles run a second copy
+        // of the cycle that can be left behind every tile: the same phases, not a tail of single tiles (that costs
+        // 2.5x the vector instructions per tile and a close of all slots).  Measured with the exits in the only
+        // copy: every tile of the sweep then pays for the block boundary at its barrier, about 5 % more cycles per
+        // tile, more than the blank tiles cost.
+        for (; t + 16 < ntiles; t += 16) {
             cycle_tile(IntC<0>(), t); cycle_tile(IntC<1>(), t); cycle_tile(IntC<2>(), t); cycle_tile(IntC<3>(), t);
             cycle_tile(IntC<4>(), t); cycle_tile(IntC<5>(), t); cycle_tile(IntC<6>(), t); cycle_tile(IntC<7>(), t);
             cycle_tile(IntC<8>(), t); cycle_tile(IntC<9>(), t); cycle_tile(IntC<10>(), t); cycle_tile(IntC<11>(), t);
             cycle_tile(IntC<12>(), t); cycle_tile(IntC<13>(), t); cycle_tile(IntC<14>(), t); cycle_tile(IntC<15>(), t);
         }
-        merge_tile(t - 4 + wave);                // the batch of the last four tiles of the last cycle
-        rcur[0][15] = kCurNone;                  // closed by the last phase, never restarted
-        // the open groups of all slots (staggered starts), before the remaining tiles
-        // start one common group
-        const int tc = t;
-        close_all([&](int rf, int r) { return max(tc - (rf ? 16 : 15) + r, 0); });
+        do {
+            if (cycle_tile(IntC<0>(), t)) break;
+            if (cycle_tile(IntC<1>(), t)) break;
+            if (cycle_tile(IntC<2>(), t)) break;
+            if (cycle_tile(IntC<3>(), t)) break;
+            if (cycle_tile(IntC<4>(), t)) break;
+            if (cycle_tile(IntC<5>(), t)) break;
+            if (cycle_tile(IntC<6>(), t)) break;
+            if (cycle_tile(IntC<7>(), t)) break;
+            if (cycle_tile(IntC<8>(), t)) break;
+            if (cycle_tile(IntC<9>(), t)) break;
+            if (cycle_tile(IntC<10>(), t)) break;
+            if (cycle_tile(IntC<11>(), t)) break;
+            if (cycle_tile(IntC<12>(), t)) break;
+            if (cycle_tile(IntC<13>(), t)) break;
+            if (cycle_tile(IntC<14>(), t)) break;
+            cycle_tile(IntC<15>(), t);
+        } while (false);
+        // State behind the last tile tl = t0 + ue (t0 the cycle's first tile, ue = tl & 15):
+        //   acc0 holds fragment 0 of tile tl + 1, a blank: dead, like g[] and b[]; live are rbest, rcur
+        //     and the seconds in LDS.
+        //   fragment 1, slot r: last closed and restarted by phase (r, 0) / (r, 1) of tile t0 + r if
+        //     r <= ue, else of tile t0 - 16 + r: its open group starts there.
+        //   fragment 0, slot r: closed by phase (r, 1), restarted one tile later: its open group starts
+        //     at t0 + r + 1 if r < ue, at t0 - 15 + r if r > ue; slot ue was closed by the last phase and
+        //     never restarted: it holds nothing.
+        //   All first tiles are clamped at 0 (first cycle: the slot has run since the segment's start).
+        //   At ue = 15 these are tc - 16 + r and tc - 15 + r of the cycle's end tc.
+        //   column partials: the in-loop merges (tiles t with (t & 3) == 1, t >= 5) have covered the tiles
+        //     up to t - 2, so everything from tf = (tl - 1) & ~3 on (clamped at 0: two to five tiles, or
+        //     all of a segment that ends before tile 5, whose throw-away merge at t = 1 has left garbage in
+        //     tiles 0 - 3) is merged here, in two rounds at most.  tf is a multiple of four, so tile T is
+        //     still merged by wave T & 3: the stores that overwrite the throw-away come from the wave that
+        //     issued it, in program order.  Five tiles fit the ring of eight.
+        //   DMA: tile_bottom has drained every load (behind a store_behind tile only stores are in flight);
+        //     the blank prefetches have landed.  The row merge below waits once more before it reuses
+        //     the tile buffers.
+        const int tl = ntiles - 1, ue = tl & 15, t0 = tl & ~15;
+        const int tf = max((tl - 1) & ~3, 0);
+        if (tf + wave_s <= tl) merge_tile(tf + wave_s);
+        if (tf + 4 + wave_s <= tl) merge_tile(tf + 4 + wave_s);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) rcur[0][r] = r == ue ? kCurNone : rcur[0][r];
+        // the open groups of all slots (staggered starts)
+        close_all([&](int rf, int r) {
+            if (rf) return r <= ue ? t0 + r : max(t0 - 16 + r, 0);
+            return r < ue ? t0 + r + 1 : r > ue ? max(t0 - 15 + r, 0) : 0;
+        });
+        t = ntiles;
+        dma_wait();
     }
     // all tiles of the kernels without the staggered schedule
     const int t_tail = t;
     if (!PIPE)
     for (; t < ntiles; ++t) {
         tile_top(t);
-        phase(IntC<0>(), IntC<-1>(), IntC<0>(), IntC<-1>(), acc0, acc1, (t & 1) ^ 1, 0, 0, 0);   // reduce (rf 0, t), produce (rf 1, t), fetch B(t+1)
-        phase(IntC<1>(), IntC<-1>(), IntC<0>(), IntC<-1>(), acc1, acc0, (t & 1) ^ 1, 0, 0, 0);   // reduce (rf 1, t), produce (rf 0, t+1)
+        phase(IntC<0>(), IntC<-1>(), IntC<0>(), IntC<-1>(), IntC<0>(), acc0, acc1, (t & 1) ^ 1, 0, 0, 0);   // reduce (rf 0, t), produce (rf 1, t), fetch B(t+1)
+        phase(IntC<1>(), IntC<-1>(), IntC<0>(), IntC<-1>(), IntC<0>(), acc1, acc0, (t & 1) ^ 1, 0, 0, 0);   // reduce (rf 1, t), produce (rf 0, t+1)
         if (PIPE ? t == ntiles - 1 : ((t % kGroupTiles) == kGroupTiles - 1 || t == ntiles - 1)) {
             const int first = PIPE ? t_tail : (t / kGroupTiles) * kGroupTiles;
             close_all([&](int, int) { return first; });
