@@ -630,6 +630,67 @@ OSFM_API int osfm_scene_filter_outliers(osfm_scene *s, osfm_outlier_stats *stats
 OSFM_API int osfm_scene_download(osfm_scene *s, uint8_t *alive_track, uint8_t *alive_feature, uint8_t *has_point, double *points);
 
 
+/* ---- initial alignment of a camera group: RANSAC over Tomasi-Kanade factorisations ----
+ *
+ * ReconstructionAlgorithm::calculateInitialAlignment (src/sfm/reconstruct.cpp:205):
+ * robustlyEstimateTomasiKanadeFactorization (src/algorithms/tomasi_kanade.cpp:193-370) over the tracks every camera
+ * of the group sees, then resolveAmbiguity (:372-444) between the two mirror solutions.  Deterministic: draw k of
+ * iteration i of group g is the counter-based generator of the RANSAC-F above under (seed, g, i, k).  Where this
+ * departs from the reference (closed-form metric upgrade, normalised coordinates, rotations as bases, the selection
+ * rule, the fallback) and why: INTEGRATION.md section 3. */
+typedef struct osfm_tk_options {
+    int32_t sample_size;        /* 10     tracks per hypothesis, 4..32 (tomasi_kanade.cpp:208) */
+    int32_t max_iterations;     /* 0      0: floor(log(1 - probability) / log(1 - inlier_ratio^sample_size)) = 241 (:212) */
+    double probability;         /* 0.999  :209 */
+    double inlier_ratio;        /* 0.7    :210 */
+    int32_t min_consensus;      /* 25     tracks outside the sample that must support a model (:221) */
+    int32_t device;             /* 0 */
+    double max_error_px;        /* 3.0    :222 */
+    uint64_t seed;              /* 0      stream seed of the counter-based sampler */
+} osfm_tk_options;
+OSFM_API int osfm_tk_options_default(osfm_tk_options *opts);
+
+enum {
+    OSFM_TK_RANSAC = 0,         /* a supported model won */
+    OSFM_TK_FALLBACK = 1,       /* no hypothesis had min_consensus: the factorisation of all given tracks (:361-365) */
+    OSFM_TK_TOO_FEW = 2,        /* fewer than max(10, sample_size) tracks (the reference throws, :202-205) */
+    OSFM_TK_DEGENERATE = 3      /* ... and the fallback's factorisation has no rank-3 / positive definite solution */
+};
+
+typedef struct osfm_tk_result {
+    int32_t status;             /* OSFM_TK_* */
+    int32_t iterations;         /* hypotheses drawn */
+    int32_t usable_models;      /* ... that factorise and pass isTomasiKanadeResultUsable (:446-470) */
+    int32_t supported_models;   /* ... and have min_consensus tracks */
+    int32_t best_iteration;     /* the winner's iteration, -1 without one */
+    int32_t num_inliers;        /* RANSAC: consensus + sample; FALLBACK: tracks within max_error_px in every camera */
+    double mean_error_px;       /* mean reprojection error of those tracks over all cameras */
+    double score_kernel_ms;     /* device time of the scoring kernel (all hypotheses x all tracks) */
+} osfm_tk_result;
+
+/* xy [num_tracks][num_cameras][2]: pixel positions, track-major, of tracks seen by every camera; 3 <= num_cameras <= 8.
+ * basis_1 / basis_2 [num_cameras][9]: the two mirror solutions, one row-major rotation per camera (columns x, y, z
+ * axis of the camera in the frame of camera 0, which is the identity); solution 1 is the one the hypotheses were
+ * scored with.  offsets [num_cameras][2] (may be NULL): the cameras' offsets that put the world origin at the
+ * centroid of the winning sample; inlier [num_tracks] (may be NULL).  opts NULL: the defaults. */
+OSFM_API int osfm_tk_align(const double *xy, int32_t num_tracks, int32_t num_cameras, int32_t img_width, int32_t img_height,
+    const osfm_tk_options *opts, uint64_t group_id, double *basis_1, double *basis_2, double *offsets, uint8_t *inlier,
+    osfm_tk_result *result);
+/* resolveAmbiguity, host only: global_rotation [num_cameras][9] row-major local -> world rotations of the group's
+ * views that have a global camera (has_global[c] != 0; the others are not read).  With a and b the first two such
+ * views, the difference of the look directions z_a - z_b in the frame where a is canonical is compared between the
+ * global pair and each model by dot product: *choice = 1 or 2, the larger; ties or fewer than two shared views: 1. */
+OSFM_API int osfm_tk_resolve_ambiguity(int32_t num_cameras, const double *basis_1, const double *basis_2,
+    const double *global_rotation, const uint8_t *has_global, int32_t *choice);
+/* osfm_tk_align on the scene's table: the live tracks seen by ALL n views (which need no cameras yet), in ascending
+ * track order, cameras in the order of `views`; selected and gathered on the device.  The views must share one image
+ * size.  *num_tracks (may be NULL): how many tracks that were; inlier (may be NULL) has capacity inlier_capacity and
+ * is written for min(*num_tracks, inlier_capacity) of them. */
+OSFM_API int osfm_scene_tk_align(osfm_scene *s, int n, const int32_t *views, const osfm_tk_options *opts, uint64_t group_id,
+    double *basis_1, double *basis_2, double *offsets, uint8_t *inlier, int32_t inlier_capacity, osfm_tk_result *result,
+    int32_t *num_tracks);
+
+
 /* The device part of orthosfm::filterTracksWithReprojectionError
  * (outlier_filtering.cpp:127-192).  p holds the FULL-SIZE tracks (the
  * caller's filterTracksToAvailableCameras(cameras, tracks, true, true)

@@ -126,6 +126,23 @@ class BaSummary(C.Structure):
                 ("chain_blocks_natural", C.c_int32), ("chain_blocks", C.c_int32)]
 
 
+class TkOptions(C.Structure):
+    """osfm_tk_options"""
+    _fields_ = [("sample_size", C.c_int32), ("max_iterations", C.c_int32), ("probability", C.c_double),
+                ("inlier_ratio", C.c_double), ("min_consensus", C.c_int32), ("device", C.c_int32),
+                ("max_error_px", C.c_double), ("seed", C.c_uint64)]
+
+
+class TkResult(C.Structure):
+    """osfm_tk_result"""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("usable_models", C.c_int32),
+                ("supported_models", C.c_int32), ("best_iteration", C.c_int32), ("num_inliers", C.c_int32),
+                ("mean_error_px", C.c_double), ("score_kernel_ms", C.c_double)]
+
+
+TK_RANSAC, TK_FALLBACK, TK_TOO_FEW, TK_DEGENERATE = 0, 1, 2, 3
+
+
 class BaLinCapture(C.Structure):
     """osfm_ba_lin_capture (test hook osfm_ba_debug_linearization)."""
     ARRAYS = ("scale_c", "diag_c", "S", "rhs", "scale_p", "diag_p", "vinv", "ge", "y_c", "cand_cams", "cand_points")
@@ -155,6 +172,7 @@ EXPORTS = [
     "osfm_scene_create", "osfm_scene_destroy", "osfm_scene_set_flags", "osfm_scene_align_views", "osfm_scene_set_cameras", "osfm_scene_get_cameras",
     "osfm_scene_triangulate", "osfm_scene_filter_reprojection", "osfm_scene_local_adjustment", "osfm_scene_global_adjustment",
     "osfm_scene_filter_outliers", "osfm_scene_download",
+    "osfm_tk_options_default", "osfm_tk_align", "osfm_tk_resolve_ambiguity", "osfm_scene_tk_align",
     "osfm_tracks_compute", "osfm_tracks_compute_ranges", "osfm_build_groups",
     "osfm_tracks_builder_create", "osfm_tracks_builder_feed", "osfm_tracks_builder_finish", "osfm_tracks_builder_destroy",
     "osfm_tracks_select_observations",

@@ -14,24 +14,12 @@
 #include <mutex>
 
 #include "ransac_kernels.h"
+#include "ransac_rand.h"
 #include "osfm_common.h"
 
 #include <algorithm>
 
 namespace osfm {
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ uint64_t ransac_rand(uint64_t seed, uint64_t pair, uint64_t it, uint64_t draw)
-{
-    return splitmix64(splitmix64(seed ^ (pair * 0xD1342543DE82EF95ull)) + it * 0x2545F4914F6CDD1Dull + draw);
-}
 
 // fundamental.cc:225-246
 __device__ __forceinline__ double

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "ba_solve.h"
+#include "tk_kernels.h"
 
 using namespace osfm;
 
@@ -976,6 +977,78 @@ int osfm_scene_global_adjustment(osfm_scene *sc, const osfm_ba_options *opt, osf
     OSFM_HIP_CHECK(hipStreamSynchronize(s));
     sum->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return OSFM_OK;
+}
+
+namespace {
+
+// coordinates of the flagged tracks' features in the camera set as rows of the Tomasi-Kanade measurement matrix:
+// rows [2n][N], column = the track's rank among the flagged ones, x rows of the n cameras, then their y rows
+__global__ void scene_tk_gather_kernel(int64_t F, int N, int n, int W, int H, const int32_t *__restrict__ in_set,
+    const int32_t *__restrict__ track_of, const int32_t *__restrict__ tflag, const int32_t *__restrict__ tslot,
+    const int32_t *__restrict__ view, const int32_t *__restrict__ cam_map, const double2 *__restrict__ xy, double *__restrict__ rows)
+{
+    const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= F || !in_set[f]) return;
+    const int t = track_of[f];
+    if (!tflag[t]) return;
+    const int c = cam_map[view[f]], j = tslot[t];
+    if (c < 0 || c >= n || j < 0 || j >= N) return;
+    const double2 p = xy[f];
+    rows[(size_t)c * N + j] = tk_normalise(p.x, W);
+    rows[(size_t)(n + c) * N + j] = tk_normalise(p.y, H);
+}
+
+}  // namespace
+
+int osfm_scene_tk_align(osfm_scene *sc, int n, const int32_t *views, const osfm_tk_options *opts, uint64_t group_id,
+    double *basis_1, double *basis_2, double *offsets, uint8_t *inlier, int32_t inlier_capacity, osfm_tk_result *result,
+    int32_t *num_tracks)
+{
+    if (!sc || !basis_1 || !basis_2 || !result || (inlier && inlier_capacity < 0)) { set_error("scene_tk_align: bad arguments"); return OSFM_E_ARG; }
+    osfm_tk_options o;
+    int iterations = 0;
+    OSFM_RETURN_IF(tk_check_options(opts, n, &o, &iterations));
+    OSFM_RETURN_IF(check_views(sc, views, n, "scene_tk_align"));
+    for (int i = 0; i < n; ++i) {
+        for (int j = 0; j < i; ++j)
+            if (views[i] == views[j]) { set_error("scene_tk_align: view %d named twice", views[i]); return OSFM_E_ARG; }
+        if (sc->img_w[views[i]] != sc->img_w[views[0]] || sc->img_h[views[i]] != sc->img_h[views[0]]) {
+            set_error("scene_tk_align: the views of a group share one image size"); return OSFM_E_ARG;
+        }
+    }
+    const int W = sc->img_w[views[0]], H = sc->img_h[views[0]];
+    std::lock_guard<std::mutex> lock(sc->mu);
+    OSFM_RETURN_IF(select_device(sc->device));
+    StreamLease sg;
+    OSFM_RETURN_IF(sg.acquire());
+    hipStream_t s = sg.s;
+    const int64_t F = sc->F;
+    const int T = sc->T;
+    int32_t *in_set = sc->sel.as<int32_t>(), *scan = sc->scan.as<int32_t>(), *cnt = sc->cnt.as<int32_t>();
+    int32_t *tflag = sc->tflag.as<int32_t>(), *tslot = sc->tslot.as<int32_t>();
+    DevArray d_views, d_rows;
+    OSFM_RETURN_IF(set_cam_map(sc, views, n, s, &d_views));
+    const int32_t *cam_map = sc->cam_map.as<int32_t>();
+    const dim3 gF(blocks_for(F + 1)), gT(blocks_for(T + 1)), b(kThreads);
+    // live features of the n views per track (the counting kernels of the reprojection filter); a track holds at
+    // most one feature per view, so a count of n is a track every view sees
+    hipLaunchKernelGGL(scene_select_kernel, gF, b, 0, s, F, sc->feat_view.as<int32_t>(), sc->track_of.as<int32_t>(),
+        sc->alive_f.as<uint8_t>(), sc->alive_t.as<uint8_t>(), cam_map, nullptr, in_set);
+    OSFM_RETURN_IF(exclusive_scan(sc, in_set, scan, F + 1, s));
+    hipLaunchKernelGGL(scene_track_count_kernel, gT, b, 0, s, T, sc->offsets.as<int32_t>(), scan, cnt);
+    hipLaunchKernelGGL(scene_track_flag_kernel, gT, b, 0, s, T, (int)kFlagCountEquals, n, cnt, nullptr, nullptr, tflag);
+    OSFM_RETURN_IF(exclusive_scan(sc, tflag, tslot, (int64_t)T + 1, s));
+    OSFM_HIP_CHECK(hipGetLastError());
+    int N = 0;
+    OSFM_RETURN_IF(read_total(tslot, T, s, &N));
+    if (num_tracks) *num_tracks = N;
+    if (N >= std::max(10, (int)o.sample_size)) {
+        OSFM_RETURN_IF(d_rows.alloc((size_t)N * n * 2 * 8));
+        hipLaunchKernelGGL(scene_tk_gather_kernel, dim3(blocks_for(F)), b, 0, s, F, N, n, W, H, in_set, sc->track_of.as<int32_t>(),
+            tflag, tslot, sc->feat_view.as<int32_t>(), cam_map, sc->feat_xy.as<double2>(), d_rows.as<double>());
+    }
+    return tk_align_core(d_rows.as<double>(), N, n, W, H, o, iterations, group_id, s, sg.ev[0].a, sg.ev[0].b, basis_1, basis_2,
+        offsets, inlier, inlier ? inlier_capacity : 0, result);
 }
 
 int osfm_scene_filter_outliers(osfm_scene *sc, osfm_outlier_stats *stats, int32_t *num_killed)

@@ -14,13 +14,19 @@ the reference calls it, timed as one job.
           filterTracksWithReprojectionError; final bundle adjustment (:281)
 
 What is NOT here, because SURVEY section 8 puts it out of scope: image IO / feature
-extraction (the synthetic ImageSet stands in for the views with their
-descriptors) and the Tomasi-Kanade initial alignment of a group
-(ReconstructionAlgorithm::calculateInitialAlignment).  The pose a new camera
-starts its local bundle adjustment from is its ground-truth pose perturbed by a
-given rotation / offset -- the role TK's estimate plays in the reference; the
-scene is expressed in the frame in which camera 0 is canonical, which is the
-frame normalizeScene (reconstruct.cpp:228,268) keeps the reconstruction in.
+extraction (the synthetic ImageSet stands in for the views with their descriptors).
+
+The initial alignment of a group (ReconstructionAlgorithm::calculateInitialAlignment,
+reconstruct.cpp:205) comes in two forms.  initial_alignment="tk": the RANSAC over
+Tomasi-Kanade factorisations of the tracks all cameras of the group see and the choice
+between its two mirror solutions against the cameras aligned so far (orthosfm_amd/tk.py,
+INTEGRATION.md section 3); every camera of the group then starts its local bundle
+adjustment from that model, in the model's own frame, and needs no pose known beforehand.
+initial_alignment="perturbed" (the default, what the benchmark and the tests of the other
+steps use): a new camera starts from its ground-truth pose perturbed by a given rotation /
+offset, cameras aligned already from their global pose; the scene is then expressed in the
+frame in which camera 0 is canonical, which is the frame normalizeScene
+(reconstruct.cpp:228,268) keeps the reconstruction in.
 
 The reference drags std::vector<Track> copies through this loop (one copy of all
 tracks per group, :205).  Here the tracks are ONE structure of arrays (features
@@ -304,6 +310,26 @@ def align_to_global(model, local, global_):
         _set_cam_rotation(model, pl, Rot @ _cam_rotation(model, pl))
 
 
+def shift_offsets_to_global(model, local, global_):
+    """After align_to_global: the local frame's origin is not the global one (a Tomasi-Kanade model puts it at the
+    centroid of its sample), and a camera's offsets are the projection of the origin.  With p_global = p_local + t a
+    camera with rotation R has offsets_global = offsets_local + (R^T t)[:2]; t is the least-squares solution of
+    those equations over the shared cameras, then applied to every local camera."""
+    o = 4 if model == B.MODEL_QUATERNION else 3
+    rows, rhs = [], []
+    for pl, pg in zip(local, global_):
+        if pg is None:
+            continue
+        Rt = _cam_rotation(model, pl).T
+        rows += [Rt[0], Rt[1]]
+        rhs += [pg[o] - pl[o], pg[o + 1] - pl[o + 1]]
+    if not rows:
+        return
+    t = np.linalg.lstsq(np.array(rows), np.array(rhs), rcond=None)[0]
+    for pl in local:
+        pl[o:o + 2] += (_cam_rotation(model, pl).T @ t)[:2]
+
+
 # ---------------------------------------------------------------------------
 # the job
 # ---------------------------------------------------------------------------
@@ -316,6 +342,7 @@ class Timings:
     tracks_busy_s: float = 0.0
     convert_s: float = 0.0
     groups_s: float = 0.0
+    initial_alignment_s: float = 0.0
     local_ba_s: float = 0.0
     local_filter_s: float = 0.0
     triangulate_s: float = 0.0
@@ -352,6 +379,7 @@ class Result:
     invalid_mve_tracks: int = 0
     captured: dict = field(default_factory=dict)
     pair_status: np.ndarray | None = None
+    initial_alignments: list = field(default_factory=list)      # one tk.Alignment per group (initial_alignment="tk")
 
 
 def _problem(model, cams, const, width, height, points, xy, obs_cam, obs_pt):
@@ -576,11 +604,17 @@ def join_background():
 
 def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2.0, off_perturb=0.01,
                         seed=7, timings=None, capture=(), max_groups=None, verbose=False, view_ids=None,
-                        euler_dof=4, check_incremental=False, use_scene=True):
-    """runPoseEstimation (reconstruct.cpp:174-295) on the track table.  use_scene: the table lives on the device
+                        euler_dof=4, check_incremental=False, use_scene=True, initial_alignment="perturbed",
+                        alignments=None):
+    """runPoseEstimation (reconstruct.cpp:174-295) on the track table.  initial_alignment: "perturbed" or "tk" (see
+    the module docstring); with "tk", group_id is the group's ordinal, seed the sampler's seed, and the groups'
+    tk.Alignment records are appended to `alignments` (a list, if given).  use_scene: the table lives on the device
     for the whole loop (osfm_scene_*: every step selects its observations there); False: every step flattens its
     tracks on the host and goes through the per-call entries of the C ABI (what a caller without the scene does;
     the two forms produce the same cameras, flags and points to the bit: tests/test_e2e_gpu.py)."""
+    if initial_alignment not in ("perturbed", "tk"):
+        raise ValueError(f"initial_alignment {initial_alignment!r}: 'perturbed' or 'tk'")
+    use_tk = initial_alignment == "tk"
     tm = timings if timings is not None else Timings()
     V = iset.num_views
     W, H = iset.width, iset.height
@@ -631,6 +665,35 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
             p[:3] += a * axis / np.sqrt(3.0)
             p[3:5] += off_perturb * rng.normal(size=2)
         return p
+
+    def tk_start(ordinal, ids):
+        """calculateInitialAlignment: all cameras of the group from the chosen Tomasi-Kanade model, in its frame."""
+        from . import tk as TK
+        t0 = time.perf_counter()
+        n = len(ids)
+        if scene is not None:
+            al = scene.tk_align(ids, group_id=ordinal, seed=seed, device=device)
+        else:
+            # the live tracks all n views see, in ascending track order, cameras in the order of ids
+            idx = tt.features_of_views(ids)
+            _, _, cnt, run = _runs(tt.track_of[idx])
+            full = cnt == n
+            fi = idx[full[run]]
+            cam_of = np.full(V, -1, dtype=np.int32)
+            cam_of[ids] = np.arange(n, dtype=np.int32)
+            xy = np.zeros((int(full.sum()), n, 2))
+            xy[(np.cumsum(full) - 1)[run][full[run]], cam_of[tt.view[fi]]] = tt.xy[fi]
+            al = TK.align(xy, W, H, group_id=ordinal, seed=seed, device=device)
+        if al.status == capi.TK_TOO_FEW:
+            raise RuntimeError(f"group {list(ids)}: too few tracks ({al.num_tracks}) for the Tomasi-Kanade alignment")
+        has_global = [bool(is_aligned[v]) for v in ids]
+        rot = np.array([_cam_rotation(model, cams[v]) if is_aligned[v] else np.eye(3) for v in ids])
+        choice = TK.resolve_ambiguity(al.basis_1, al.basis_2, rot, has_global)
+        if alignments is not None:
+            alignments.append(al)
+        lp = TK.bases_to_params(model, al.basis_1 if choice == 1 else al.basis_2)
+        tm.initial_alignment_s += time.perf_counter() - t0
+        return lp
 
     def solve(kind, prob, options):
         t0 = time.perf_counter()
@@ -738,7 +801,7 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
             processed += 1
             ids = list(g.ids)
             first_group = not aligned
-            lp = np.array([cams[v].copy() if is_aligned[v] else start_pose(v) for v in ids])
+            lp = tk_start(processed - 1, ids) if use_tk else np.array([cams[v].copy() if is_aligned[v] else start_pose(v) for v in ids])
             lc = np.array([default_const_mask(model, euler_dof=euler_dof) for _ in ids])
             if first_group:
                 lc[0] = default_const_mask(model, fixed=True, euler_dof=euler_dof)
@@ -755,6 +818,8 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
                 scene.align_views(new_views, cams[new_views], const[new_views])
             else:
                 align_to_global(model, lp, [cams[v] if is_aligned[v] else None for v in ids])
+                if use_tk:
+                    shift_offsets_to_global(model, lp, [cams[v] if is_aligned[v] else None for v in ids])
                 for k, v in enumerate(ids):
                     if not is_aligned[v]:
                         cams[v] = lp[k]; const[v] = default_const_mask(model, euler_dof=euler_dof)
@@ -809,8 +874,8 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
         processed += 1
         ids = list(g.ids)
         first_group = not aligned
-        # ---- calculateInitialAlignment (stand-in, see the module docstring) -------
-        lp = np.array([cams[v].copy() if is_aligned[v] else start_pose(v) for v in ids])
+        # ---- calculateInitialAlignment (see the module docstring) -------
+        lp = tk_start(processed - 1, ids) if use_tk else np.array([cams[v].copy() if is_aligned[v] else start_pose(v) for v in ids])
         lc = np.array([default_const_mask(model, euler_dof=euler_dof) for _ in ids])
         if first_group:
             lc[0] = default_const_mask(model, fixed=True, euler_dof=euler_dof)          # localCameras[0]->setFixed(true), :215
@@ -835,6 +900,8 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
             triangulate_all()
         else:
             align_to_global(model, lp, [cams[v] if is_aligned[v] else None for v in ids])
+            if use_tk:
+                shift_offsets_to_global(model, lp, [cams[v] if is_aligned[v] else None for v in ids])
             new_views = []
             for k, v in enumerate(ids):                             # mergeIntoGlobal: only the new cameras
                 if not is_aligned[v]:
@@ -894,7 +961,7 @@ def _global_ba(tt, model, cams, const, aligned, W, H, V, solve, kind, opt, tm):
 
 def reconstruct(iset, solver=0, matcher="exhaustive", device=0, verify=True, rot_perturb_deg=2.0,
                 off_perturb=0.01, seed=7, capture=(), max_groups=None, verbose=False,
-                check_incremental=False, use_scene=True) -> Result:
+                check_incremental=False, use_scene=True, initial_alignment="perturbed") -> Result:
     """orthosfm::reconstruct from the views' descriptors on: one wall clock over matching,
     track building, group ordering and the incremental pose estimation.
     solver 0: quaternion cameras (ORTHO_QUATERNION); 1..3: Euler cameras with that many
@@ -903,13 +970,15 @@ def reconstruct(iset, solver=0, matcher="exhaustive", device=0, verify=True, rot
     t_all = time.perf_counter()
     tt, info = match_and_build_tracks(iset, matcher, device, verify, tm)
     model = B.MODEL_QUATERNION if solver == 0 else B.MODEL_EULER
+    alignments = []
     cams, aligned, groups, calls, captured = run_pose_estimation(
         tt, iset, model, device, rot_perturb_deg, off_perturb, seed, tm, capture, max_groups, verbose,
-        euler_dof=euler_dof_of_solver(solver), check_incremental=check_incremental, use_scene=use_scene)
+        euler_dof=euler_dof_of_solver(solver), check_incremental=check_incremental, use_scene=use_scene,
+        initial_alignment=initial_alignment, alignments=alignments)
     join_background()            # inside the clock: the matcher's memory is back when the job is done
     tm.total_s = time.perf_counter() - t_all
     info.pop("match_stats", None)
-    return Result(cams, aligned, tt, groups, tm, calls, captured=captured, **info)
+    return Result(cams, aligned, tt, groups, tm, calls, captured=captured, initial_alignments=alignments, **info)
 
 
 CAMERA_DISTANCE = 10.0                  # OrthoQuaternionCamera.cpp:70, OrthographicCamera.h:119

@@ -94,6 +94,22 @@ class Scene:
                                                         C.byref(m), C.byref(o)))
         return s, m.value, o.value
 
+    def tk_align(self, views, group_id=0, **opts):
+        """osfm_scene_tk_align: the Tomasi-Kanade RANSAC (orthosfm_amd/tk.py) over the live tracks that all `views`
+        see, selected and gathered on the device; cameras in the order of `views`."""
+        from . import tk
+        v = np.ascontiguousarray(views, dtype=np.int32)
+        c = int(v.shape[0])
+        o = tk.options(**opts)
+        b1, b2, off = np.zeros((max(c, 1), 3, 3)), np.zeros((max(c, 1), 3, 3)), np.zeros((max(c, 1), 2))
+        inl = np.zeros(max(self.num_tracks, 1), dtype=np.uint8)
+        r, n = capi.TkResult(), C.c_int32()
+        capi.check(capi.lib.osfm_scene_tk_align(self._h_scene, C.c_int(c), capi._ptr(v, C.c_int32), C.byref(o),
+                                                C.c_uint64(group_id), capi._ptr(b1, C.c_double), capi._ptr(b2, C.c_double),
+                                                capi._ptr(off, C.c_double), capi._ptr(inl, C.c_uint8),
+                                                C.c_int32(inl.shape[0]), C.byref(r), C.byref(n)))
+        return tk._alignment(b1, b2, off, inl, r, n.value)
+
     def global_adjustment(self, options):
         s = capi.BaSummary()
         m, o = C.c_int32(), C.c_int32()
