@@ -855,7 +855,9 @@ done:
 /* B8: triangulateOrthographicTracks + intersectRays
  * (src/triangulation/triangulation.cpp:11-93) with the camera accessors
  * getPointOnCameraPlane / getLookDirection
- * (OrthoQuaternionCamera.cpp:45-59, OrthographicCamera.cpp:63-95,187-193).  */
+ * (OrthoQuaternionCamera.cpp:45-59, OrthographicCamera.cpp:63-95,187-193).
+ * This section is a line-for-line twin of ba_triangulate_kernel (ba_kernels.hip), so a mistake the two share
+ * passes a comparison of one with the other; the independent check is tests/test_triangulation_gpu.py.  */
 
 static void quat_rot(const double *q, const double v[3], double out[3])
 {

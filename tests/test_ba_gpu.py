@@ -39,6 +39,8 @@ def test_reprojection_errors(ba, model):
 
 @pytest.mark.parametrize("model", [0, 1])
 def test_triangulation(ba, model):
+    """The oracle is a line-for-line twin of the kernel here, so this holds the two together and no more; the
+    independent check, against a 200-bit reference with a bound per track, lives in test_triangulation_gpu.py."""
     sc = synth.make_ba_scene(model, 9, 400, config_id=32, noise_px=0.3)
     ref = sc.copy()
     evalid = oracle_lib.oracle_ba_triangulate(ref)
