@@ -1280,21 +1280,71 @@ void launch_match_finish(const MatchProblem *d_problems, int num_problems, int m
 constexpr int kRescorePerWave = 16;
 static_assert(2 * (kRescoreWin + 15) <= 64, "a direction-0 bucket's candidates fill two MFMA blocks at most");
 
-// (four waves per SIMD: the kernel is a chain of dependent loads per bucket, what hides it is waves)
+// What the kernel knows of a bucket before it loads anything of it (wave-uniform, scalar registers).
+struct RescoreBucket {
+    int live;           // 0: there is no such bucket -- its loads are still issued (no branch) and read one valid line each
+    int p;              // problem
+    int dir, cnt;
+    int base, step, limit;      // candidate of slot o: base + step * o where that is below limit
+    int64_t item0;      // its first item in rs_items
+};
+
+// candidate of slot o (0..63) of a bucket, -1 for none -- the masks of rescan_groups
+//   dir 1: row  strip + o                      (strip = first row of the 64-row strip)
+//   dir 0: column 64 (w0 + o / 2) + 32 (o & 1) + lr = 64 w0 + lr + 32 o   (w0 = first tile of the window)
+static_assert(kTileCols == 64, "a direction-0 bucket's candidates are 32 columns apart");
+__device__ __forceinline__ int
+rescore_cand(const RescoreBucket &B, int o)
+{
+    const int c = B.base + B.step * o;
+    return c < B.limit ? c : -1;
+}
+
+template <class T>
+__device__ __forceinline__ const __attribute__((address_space(1))) T *
+as_global(const T *p) { return (const __attribute__((address_space(1))) T *)p; }
+
+// Four waves per SIMD, and on top of them the whole next bucket in flight behind the one being scored.  A bucket
+// used to be one chain -- count, problem fields, items and candidates, query rows, MFMAs -- started when the
+// bucket before it was done.  Now bucket i + 1 is requested while bucket i is scored, all of it:
+//   its 64 candidate rows    LDS DMA, 16 B per lane, eight instructions for the 8 KB, into the wave's own slot;
+//   its candidate corrections and the rows and corrections of its first 32 queries: ordinary loads (22 registers);
+//   the first 32 items of bucket i + 2: DMA, one dword per lane -- the query gather needs a bucket's items one
+//   bucket ahead of the bucket itself.
+// The walk to the next problem runs two buckets ahead, on scalars.  The order inside a bucket makes room: the
+// MFMAs come first, straight behind the switch, and the requests go out when they are done -- the A operands
+// (which cannot be held twice: 32 registers, 126 of 128 were in use) and the query rows are dead by then, the
+// slot is free for the DMA, and what overlaps the loads is the epilogue, the longer half.  The one wait is the
+// switch, and it is for everything: nothing inside a bucket waits for part of what is in flight.
+// The DMA is inline assembly with m0 written behind the compiler's back, as in the tile kernel (hipcc rejects m0
+// as a clobber; nothing else here uses m0, tools/check_m0.sh looks at the ISA): through the builtin the compiler
+// marks the wave as having a flat access pending and turns every later wait into a wait for everything, the
+// scalar loads of the problem fields included.  It writes LDS linearly, an instruction carries eight whole rows,
+// and a row's chunks are XOR-swizzled by the SOURCE address, so that the fragment reads are conflict-free (as in
+// match_special_kernel).  Every request is issued for every bucket, also behind the wave's last one (all lanes
+// then read one line): a branch around them would only add a path.
 __global__ __launch_bounds__(256, 4) void
 match_rescore_kernel(const MatchProblem *__restrict__ problems, int num_problems, const int32_t *__restrict__ rs_count,
     const RescoreItem *__restrict__ rs_items, int total_buckets, int total_blocks, LoweTable tab,
     ExactItem *__restrict__ exact_items, int32_t *__restrict__ exact_count, int exact_cap)
 {
     __shared__ __attribute__((aligned(16))) int corr_s[4][64];
+    __shared__ __attribute__((aligned(16))) int8_t cand_s[4][64 * 128];       // the next bucket's candidates, per wave
+    __shared__ __attribute__((aligned(16))) RescoreItem items_s[4][2][32];    // the first items of the next two buckets
+    __shared__ int cnt_s[4][kRescorePerWave];                                  // the counts of the wave's buckets (read two buckets ahead: not worth a register)
+    static_assert(kRescoreCap0 >= 32 && kRescoreCap1 >= 32, "32 items are read of every bucket");
     // consecutive workgroups (one problem's buckets) on one XCD: its descriptors are fetched into one L2
     const int lin = xcd_remap(blockIdx.x, total_blocks);
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
+    // (the wave's number as a scalar: the buckets, their problems and everything derived from them then stay in
+    //  scalar registers, and the problem fields come through the scalar cache)
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
     const int b0 = (lin * 4 + wv) * kRescorePerWave;
     if (b0 >= total_buckets) return;
     const int cnt_l = lane < kRescorePerWave && b0 + lane < total_buckets ? rs_count[b0 + lane] : 0;
     unsigned long long todo = __ballot(cnt_l > 0);
     if (!todo) return;
+    if (lane < kRescorePerWave) cnt_s[wv][lane] = cnt_l;
+    __builtin_amdgcn_wave_barrier();
     // the problem of the first live bucket (largest p with rs_bucket_off <= b); later ones by stepping
     int p = 0;
     {
@@ -1306,8 +1356,11 @@ match_rescore_kernel(const MatchProblem *__restrict__ problems, int num_problems
         }
         p = lo;
     }
-    const v16i zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    while (todo) {
+    // the next live bucket of the run (in ascending order: p only steps forward), or a dead copy of `last`
+    auto describe_next = [&](const RescoreBucket &last) __attribute__((always_inline)) {
+        RescoreBucket B = last;
+        B.live = 0;
+        if (!todo) return B;
         const int k = __ffsll((long long)todo) - 1;
         todo &= todo - 1;
         const int b = b0 + k;
@@ -1315,68 +1368,103 @@ match_rescore_kernel(const MatchProblem *__restrict__ problems, int num_problems
         const MatchProblem &pd = problems[p];
         const int local = b - (int)pd.rs_bucket_off;
         const int nb1 = pd.nrb_main * 4;
-        const int dir = local < nb1 ? 1 : 0;
-        // candidate of slot o (0..63), -1 for none -- the masks of rescan_groups
-        //   dir 1: row  strip + o                      (strip = first row of the 64-row strip)
-        //   dir 0: column 64 (w0 + o / 2) + 32 (o & 1) + lr   (w0 = first tile of the window)
-        int strip = 0, w0 = 0, lr = 0, cap;
-        int64_t item0;
-        if (dir == 1) {
-            strip = (local >> 2) * kRowsPerBlock + (local & 3) * 64;
+        B.live = 1; B.p = p;
+        B.dir = local < nb1 ? 1 : 0;
+        int cap;
+        if (B.dir == 1) {
+            B.base = (local >> 2) * kRowsPerBlock + (local & 3) * 64; B.step = 1; B.limit = pd.n1;
             cap = kRescoreCap1;
-            item0 = pd.rs_item_off + (int64_t)local * kRescoreCap1;
+            B.item0 = pd.rs_item_off + (int64_t)local * kRescoreCap1;
         } else {
             const int l0 = local - nb1;
-            w0 = (l0 >> 5) * kRescoreWin; lr = l0 & 31;
+            B.base = kTileCols * ((l0 >> 5) * kRescoreWin) + (l0 & 31); B.step = 32; B.limit = pd.n2;
             cap = kRescoreCap0;
-            item0 = pd.rs_item_off + (int64_t)nb1 * kRescoreCap1 + (int64_t)l0 * kRescoreCap0;
+            B.item0 = pd.rs_item_off + (int64_t)nb1 * kRescoreCap1 + (int64_t)l0 * kRescoreCap0;
         }
-        auto cand_of = [&](int o) {
-            if (dir == 1) { const int r = strip + o; return r < pd.n1 ? r : -1; }
-            const int c = kTileCols * (w0 + (o >> 1)) + 32 * (o & 1) + lr;
-            return c < pd.n2 ? c : -1;
-        };
-        const int cnt = min(__builtin_amdgcn_readlane(cnt_l, k), cap);
-        const int8_t *Cm = dir == 0 ? pd.B : pd.A;
-        const int8_t *Qm = dir == 0 ? pd.A : pd.B;
-        const int32_t *corrC = dir == 0 ? pd.corrB : pd.corrA;
-        const int32_t *corrQ = dir == 0 ? pd.corrA : pd.corrB;
+        B.cnt = min(__builtin_amdgcn_readfirstlane(cnt_s[wv][k]), cap);
+        return B;
+    };
+    // a bucket's first 32 items, 64 dwords, one per lane (what lies behind cnt is masked where they are read)
+    auto fetch_items = [&](const RescoreBucket &B, int buf) __attribute__((always_inline)) {
+        const RescoreItem *src = rs_items + B.item0;                                    // uniform
+        const unsigned lds_at = (unsigned)(uintptr_t)&items_s[wv][buf][0];
+        asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dword %0, %1" :: "v"(lane * 4), "s"(src), "s"(lds_at) : "memory");
+    };
+    // its candidates: LDS chunk q = c * 64 + lane holds chunk (q % 8) ^ swz(d) of slot d = q / 8.  A slot without
+    // candidate reads the bucket's last one (masked through its correction); the offsets are taken from the
+    // bucket's first candidate, which exists, so that they fit 32 bits whatever the size of the set.
+    auto fetch_cands = [&](const RescoreBucket &B) __attribute__((always_inline)) {
+        const MatchProblem &pd = problems[B.p];
+        // (a live bucket's first candidate exists -- a query's winning group lies in it; the clamps keep the
+        //  addresses inside the set whatever the counts say)
+        const int first = max(min(B.base, B.limit - 1), 0);
+        const int8_t *src = (B.dir == 0 ? pd.B : pd.A) + (size_t)first * 128;              // uniform
+        const int span = max(B.limit - 1 - first, 0) & -B.live;                          // no bucket: its first row for every lane
+        const int chunk_mask = 7 & -B.live;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const int d = 8 * c + (lane >> 3);
+            const unsigned off = (unsigned)min(B.step * d, span) * 128u + (unsigned)((((lane & 7) ^ ((d >> 1) & 7)) & chunk_mask) * 16);
+            const unsigned lds_at = (unsigned)(uintptr_t)&cand_s[wv][c * 1024];
+            asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(off), "s"(src), "s"(lds_at) : "memory");
+        }
+    };
+    const v16i zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // what is held of the next bucket in registers: the first 32 queries' items, rows and corrections, and the
+    // correction of candidate slot `lane` (as loaded: its mask is applied at the switch)
+    RescoreItem itn;
+    v4i bqn[4];
+    int cqn, corr_n;
+    auto fetch_queries = [&](const RescoreBucket &B, int buf) __attribute__((always_inline)) {
+        const MatchProblem &pd = problems[B.p];
+        itn = items_s[wv][buf][j];
+        if (j >= (B.cnt & -B.live)) { itn.q_sub = 0; itn.ip2 = 0; }
+        const int q = itn.q_sub >> 5;
+        const int8_t *Qm = B.dir == 0 ? pd.A : pd.B;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks)      // (global, not flat: a flat load also counts as an LDS access)
+            bqn[ks] = *as_global(reinterpret_cast<const v4i *>(Qm + (size_t)q * 128 + (ks * 2 + h) * 16));
+        cqn = *as_global((B.dir == 0 ? pd.corrA : pd.corrB) + q);
+        corr_n = *as_global((B.dir == 0 ? pd.corrB : pd.corrA) + (max(rescore_cand(B, lane), 0) & -B.live));
+    };
+    // everything in flight has arrived, in the compiler's books as well
+    auto arrived = [&]() __attribute__((always_inline)) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(bqn[ks]));
+        asm volatile("" : "+v"(cqn), "+v"(corr_n) :: "memory");
+    };
+    RescoreBucket none;
+    none.live = 0; none.p = 0; none.dir = 0; none.cnt = 0; none.base = 0; none.step = 0; none.limit = 1; none.item0 = 0;
+    RescoreBucket cur = describe_next(none), nx1 = describe_next(cur), nx2 = nx1;
+    // the first bucket's items, then (they are needed for the gather) everything else of it
+    fetch_items(cur, 0);
+    fetch_items(nx1, 1);
+    fetch_cands(cur);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    fetch_queries(cur, 0);
+    for (int par = 0;; par ^= 1) {
+        const MatchProblem &pd = problems[cur.p];
+        const int dir = cur.dir, cnt = cur.cnt;
+        auto cand_of = [&](int o) __attribute__((always_inline)) { return rescore_cand(cur, o); };
         int32_t *out = dir == 0 ? pd.m12 : pd.m21;
-        // the first block's items before the candidates: the query loads that depend on them are then
-        // one memory latency behind, not two
-        RescoreItem it0;
-        it0.q_sub = 0; it0.ip2 = 0;
-        if (j < cnt) it0 = rs_items[item0 + j];
+        // The switch: nothing below may be moved above this point.
+        arrived();
         // the candidates: slot 32 bk + j of lane half h holds bytes (2 ks + h) * 16 .. +16 in k-step ks
         // (the tile kernel's operand order; the B operand below uses the same one)
         v4i a[2][4];
-#pragma unroll
-        for (int bk = 0; bk < 2; ++bk) {
-            const int cs = max(cand_of(32 * bk + j), 0);       // no candidate: row 0, masked below
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                a[bk][ks] = *reinterpret_cast<const v4i *>(Cm + (size_t)cs * 128 + (ks * 2 + h) * 16);
-        }
         {
-            const int c = cand_of(lane);
-            // INT_MIN marks a slot without candidate (corrections stay far from it)
-            corr_s[wv][lane] = c >= 0 ? corrC[c] : INT_MIN;
-        }
-        __builtin_amdgcn_wave_barrier();
-        for (int qb = 0; qb < cnt; qb += 32) {
-            const bool live = qb + j < cnt;
-            RescoreItem it = it0;
-            if (qb > 0) {
-                it.q_sub = 0; it.ip2 = 0;
-                if (live) it = rs_items[item0 + qb + j];
-            }
-            const int q = it.q_sub >> 5, sub = it.q_sub & 31;
-            v4i bq[4];
+            const int swz = (j >> 1) & 7;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                bq[ks] = *reinterpret_cast<const v4i *>(Qm + (size_t)q * 128 + (ks * 2 + h) * 16);
-            const int cq = corrQ[q];
-            v16i acc[2];
+            for (int bk = 0; bk < 2; ++bk)
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks)
+                    a[bk][ks] = *reinterpret_cast<const v4i *>(&cand_s[wv][(32 * bk + j) * 128 + (((ks * 2 + h) ^ swz) * 16)]);
+        }
+        // INT_MIN marks a slot without candidate (corrections stay far from it)
+        corr_s[wv][lane] = cand_of(lane) >= 0 ? corr_n : INT_MIN;
+        __builtin_amdgcn_wave_barrier();
+        auto multiply = [&](const v4i (&bq)[4], v16i (&acc)[2]) __attribute__((always_inline)) {
 #pragma unroll
             for (int bk = 0; bk < 2; ++bk) {
                 acc[bk] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[bk][0], bq[0], zero16, 0, 0, 0);
@@ -1384,13 +1472,22 @@ match_rescore_kernel(const MatchProblem *__restrict__ problems, int num_problems
                 for (int ks = 1; ks < 4; ++ks)
                     acc[bk] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[bk][ks], bq[ks], acc[bk], 0, 0, 0);
             }
+        };
+        // 32 queries' scores against the bucket: everything behind the MFMAs
+        auto finish_block = [&](int qb, const RescoreItem it, int cq, const v16i (&acc)[2]) __attribute__((always_inline)) {
+            // (the lane half as a value of this bucket: taken from outside the loop, the 32 slot numbers that depend
+            //  on it are kept in registers through everything else)
+            int hl = h;
+            asm volatile("" : "+v"(hl));
+            const bool live = qb + j < cnt;
+            const int q = it.q_sub >> 5, sub = it.q_sub & 31;
             // keys of the query's own candidates: distinct, so (best, second) is a max / med3 pair
             int kbest = INT_MIN, ksec = INT_MIN;
 #pragma unroll
             for (int bk = 0; bk < 2; ++bk)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const int ob = 32 * bk + 8 * g + 4 * h;           // slots ob .. ob + 3
+                    const int ob = 32 * bk + 8 * g + 4 * hl;          // slots ob .. ob + 3
                     const v4i cc = *reinterpret_cast<const v4i *>(&corr_s[wv][ob]);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -1400,7 +1497,7 @@ match_rescore_kernel(const MatchProblem *__restrict__ problems, int num_problems
                         if (dir == 1) {
                             // o = 32 (n >> 4) + (r & 3) + 8 (r >> 2) + 4 half, r = n & 15
                             n = 16 * bk + 4 * g + e;
-                            ok = h == sub;
+                            ok = hl == sub;
                         } else {
                             // o = 2 (tile - first tile of the group) + column half
                             n = o - 2 * sub;
@@ -1415,27 +1512,77 @@ match_rescore_kernel(const MatchProblem *__restrict__ problems, int num_problems
             const int obest = __shfl_xor(kbest, 32), osec = __shfl_xor(ksec, 32);
             const int wbest = max(kbest, obest);
             const int wsec = max(min(kbest, obest), max(ksec, osec));
-            if (live && h == 0) {
+            if (live && hl == 0) {
                 const int pos = wbest & 31;
                 const int o = dir == 1 ? 32 * (pos >> 4) + (pos & 3) + 8 * ((pos >> 2) & 3) + 4 * sub : pos + 2 * sub;
                 const int idx = max(cand_of(o), 0);
                 const int rbest = wbest >> 5;
                 const int rsecond = max(wsec == INT_MIN ? INT_MIN : wsec >> 5, it.ip2);
                 const int res = accept_match(rbest, rsecond, idx, tab);
-                out[q] = res;
+                *(__attribute__((address_space(1))) int32_t *)(out + q) = res;
                 // accepted although two candidates tie for best: the sequential scan decides
                 if (res >= 0 && rsecond == rbest) {
                     const int slot = atomicAdd(exact_count, 1);
                     if (slot < exact_cap) {
                         ExactItem e;
-                        e.problem = p; e.dir = dir; e.query = q;
+                        e.problem = cur.p; e.dir = dir; e.query = q;
                         exact_items[slot] = e;
                     }
                 }
             }
+        };
+        const RescoreItem it0 = itn;
+        const int cq0 = cqn;
+        v16i acc0[2];
+        multiply(bqn, acc0);
+        // The requests of the next bucket.  The A operands have been read (the MFMAs have issued with them), so
+        // the slot is free; the items of the bucket after next take the buffer this bucket's came from.
+        auto request_next = [&]() __attribute__((always_inline)) {
+            __builtin_amdgcn_sched_barrier(0);
+            nx2 = describe_next(nx1);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            fetch_cands(nx1);
+            fetch_items(nx2, par);
+            fetch_queries(nx1, par ^ 1);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        if (cnt <= 32) {
+            request_next();
+            finish_block(0, it0, cq0, acc0);
+        } else {
+            // a bucket with more than 32 queries (rare) is finished before anything is requested: its further
+            // blocks need the A operands, their items and rows come straight from memory
+            finish_block(0, it0, cq0, acc0);
+            const int8_t *Qm = dir == 0 ? pd.A : pd.B;
+            const int32_t *corrQ = dir == 0 ? pd.corrA : pd.corrB;
+            for (int qb = 32; qb < cnt; qb += 32) {
+                RescoreItem it;
+                it.q_sub = 0; it.ip2 = 0;
+                int jj = j;
+                asm volatile("" : "+v"(jj));      // (its address is not worth two registers held through the common path)
+                if (qb + jj < cnt) {
+                    typedef int item_words __attribute__((ext_vector_type(2)));
+                    const item_words w = *as_global(reinterpret_cast<const item_words *>(rs_items + cur.item0 + qb + jj));
+                    it.q_sub = w.x; it.ip2 = w.y;
+                }
+                const int q = it.q_sub >> 5;
+                v4i bq[4];
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks)
+                    bq[ks] = *as_global(reinterpret_cast<const v4i *>(Qm + (size_t)q * 128 + (ks * 2 + h) * 16));
+                const int cq = *as_global(corrQ + q);
+                v16i acc[2];
+                multiply(bq, acc);
+                finish_block(qb, it, cq, acc);
+            }
+            request_next();
         }
         __builtin_amdgcn_wave_barrier();    // corr_s is rewritten by the next bucket
+        if (!nx1.live) break;
+        cur = nx1; nx1 = nx2;
     }
+    // (the requests of the dead bucket behind the last one are still in flight: they land in this wave's own slots)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 void launch_match_rescore(const MatchProblem *d_problems, int num_problems, const int32_t *rs_count,
