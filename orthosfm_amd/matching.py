@@ -202,7 +202,8 @@ class HipExhaustiveMatching:
 
     @staticmethod
     def ransac_fundamental(pos1, pos2, corr, max_iterations=1000, threshold=0.0015, seed=0, pair_id=0, device=0):
-        """sfm::RansacFundamental::estimate for one pair; returns (inlier ids, F)."""
+        """sfm::RansacFundamental::estimate for one pair; returns (count, inlier ids, F): the number of
+        inliers (-1 below 8 matches), their ascending indices into corr and the 3x3 F of the winning hypothesis."""
         pos1 = np.ascontiguousarray(pos1, dtype=np.float32).reshape(-1, 2)
         pos2 = np.ascontiguousarray(pos2, dtype=np.float32).reshape(-1, 2)
         corr = np.ascontiguousarray(corr, dtype=np.int32).reshape(-1, 2)

@@ -1,6 +1,9 @@
 """GPU tests of the geometric verification row (RANSAC-F) through the C ABI,
 against the CPU oracle: same counter-based sample stream and the same double
-arithmetic in the same order, so inlier sets and F agree bit for bit."""
+arithmetic in the same order, so inlier sets and F agree bit for bit.  The oracle is
+the kernel's twin: a mistake made in both passes here.  The independent check -- an exact
+null vector, a 200-bit rank-2 step and banded Sampson counts, at the sizes where the kernel
+changes path -- is tests/test_ransac_paths_gpu.py (cases and reference: tests/ransac_cases.py)."""
 import numpy as np
 import pytest
 
