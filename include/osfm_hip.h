@@ -881,6 +881,72 @@ OSFM_API int osfm_sparse_cloud_write(const char *path, int64_t num_tracks,
 OSFM_API int osfm_time_measurements_write(const char *path, const double *seconds);
 OSFM_API int osfm_time_measurements_read(const char *path, double *seconds);
 
+/* ---------------------------------------------------------------------------
+ * SIFT feature extraction (MVE's sfm/sift.cc and FeatureSet::compute_sift,
+ * feature_set.cc:42-86), on the device.  The octave and DoG images, the candidate
+ * list and the localised keypoints are equal to the reference's bytes; orientations
+ * and descriptors are the same algorithm evaluated in double (DESIGN.md has the
+ * measured distance).  Image files, the max_image_size halving loop of
+ * bundler_features.cc:66-68 and SURF stay with the caller.
+ * ------------------------------------------------------------------------- */
+#define OSFM_SIFT_MAX_OCTAVES 16
+
+/* Sift::Options and the capacity of a context's candidate and descriptor arrays. */
+typedef struct osfm_sift_options {
+    int32_t num_samples_per_octave;   /* 3 */
+    int32_t min_octave;               /* 0, or -1: an octave of the doubled image first (values above 0 are refused) */
+    int32_t max_octave;               /* 4 */
+    float contrast_threshold;         /* negative: 0.02 / num_samples_per_octave */
+    float edge_ratio_threshold;       /* 10 */
+    float base_blur_sigma;            /* 1.6 */
+    float inherent_blur_sigma;        /* 0.5 */
+    int32_t max_keypoints;            /* 65536: more candidates or more descriptors than this is OSFM_E_CAPACITY */
+} osfm_sift_options;
+OSFM_API int osfm_sift_options_default(osfm_sift_options *opts);
+
+typedef struct osfm_sift_summary {
+    int32_t num_candidates, num_keypoints, num_descriptors, num_octaves;
+    int32_t keypoints_per_octave[OSFM_SIFT_MAX_OCTAVES];     /* entry 0 is octave min_octave */
+    int32_t descriptors_per_octave[OSFM_SIFT_MAX_OCTAVES];
+    /* stage times from events on the context's stream; localisation includes the keypoints' way to the host */
+    double scale_space_ms, extrema_ms, localisation_ms, orientation_ms, descriptor_ms, total_ms;
+} osfm_sift_summary;
+
+typedef struct osfm_sift osfm_sift;
+
+/* A context owns the pyramid and the work arrays for images up to max_width x max_height (booked in
+ * osfm_library_memory as device_buffer_bytes) and serves one extraction at a time.  opts NULL: the defaults. */
+OSFM_API int osfm_sift_create(int device, int max_width, int max_height, const osfm_sift_options *opts, osfm_sift **out);
+OSFM_API int osfm_sift_destroy(osfm_sift *ctx);
+
+/* Extracts the features of an 8-bit image in host memory, row-major, channels interleaved; 3 channels are
+ * averaged (DESATURATE_AVERAGE).  On success the context holds the result until the next call and *summary
+ * (may be NULL) is filled.  Errors, none of which writes *summary or leaves a result behind:
+ *   OSFM_E_ARG       channels other than 1 or 3; a size on which the reference throws (create_octaves halves
+ *                    the image once per octave, the last included, and halving needs 2 pixels a side)
+ *   OSFM_E_RANGE     an image larger than the context
+ *   OSFM_E_CAPACITY  more candidates or more descriptors than max_keypoints -- never a truncated result */
+OSFM_API int osfm_sift_extract(osfm_sift *ctx, const uint8_t *pixels, int width, int height, int channels,
+    osfm_sift_summary *summary);
+
+/* The result of the last extraction in FeatureSet's order: by scale descending, descriptors of equal scale in
+ * the order the detector generated them (the reference's std::sort leaves those unordered).  Every output is
+ * caller-allocated for num_descriptors rows and may be NULL.
+ *   descriptors [n][128], positions [n][2] (x, y in pixels of the input image), scale [n], orientation [n],
+ *   colors [n][3] (linear_at on the byte image; a grey image gives its value three times),
+ *   normalized_positions [n][2] (normalize_feature_positions with the principal point at 0.5, 0.5) */
+OSFM_API int osfm_sift_download(osfm_sift *ctx, float *descriptors, float *positions, float *scale, float *orientation,
+    uint8_t *colors, float *normalized_positions);
+
+/* Test hooks.  osfm_sift_debug_image: image `index` of octave `octave` (min_octave .. max_octave) of the last
+ * extraction; kind 0: the S + 3 octave images, kind 1: the S + 2 DoG images.  *width / *height (may be NULL)
+ * are always set; out (may be NULL) takes width * height floats.
+ * osfm_sift_debug_keypoints: rows (octave, sample, x, y) of the candidates (after_localisation 0) or of the
+ * localised keypoints (1), in the detector's order; *count (may be NULL) is always set, out may be NULL. */
+OSFM_API int osfm_sift_debug_image(osfm_sift *ctx, int octave, int kind, int index, float *out, int32_t *width,
+    int32_t *height);
+OSFM_API int osfm_sift_debug_keypoints(osfm_sift *ctx, int after_localisation, float *out, int32_t *count);
+
 #ifdef __cplusplus
 }
 #endif

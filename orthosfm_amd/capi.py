@@ -142,6 +142,25 @@ class TkResult(C.Structure):
 
 TK_RANSAC, TK_FALLBACK, TK_TOO_FEW, TK_DEGENERATE = 0, 1, 2, 3
 
+SIFT_MAX_OCTAVES = 16
+
+
+class SiftOptions(C.Structure):
+    """osfm_sift_options"""
+    _fields_ = [("num_samples_per_octave", C.c_int32), ("min_octave", C.c_int32), ("max_octave", C.c_int32),
+                ("contrast_threshold", C.c_float), ("edge_ratio_threshold", C.c_float),
+                ("base_blur_sigma", C.c_float), ("inherent_blur_sigma", C.c_float), ("max_keypoints", C.c_int32)]
+
+
+class SiftSummary(C.Structure):
+    """osfm_sift_summary"""
+    _fields_ = [("num_candidates", C.c_int32), ("num_keypoints", C.c_int32), ("num_descriptors", C.c_int32),
+                ("num_octaves", C.c_int32),
+                ("keypoints_per_octave", C.c_int32 * SIFT_MAX_OCTAVES),
+                ("descriptors_per_octave", C.c_int32 * SIFT_MAX_OCTAVES)] + \
+               [(n, C.c_double) for n in ("scale_space_ms", "extrema_ms", "localisation_ms", "orientation_ms",
+                                          "descriptor_ms", "total_ms")]
+
 
 class BaLinCapture(C.Structure):
     """osfm_ba_lin_capture (test hook osfm_ba_debug_linearization)."""
@@ -180,6 +199,8 @@ EXPORTS = [
     "osfm_tracks_file_write", "osfm_tracks_file_read", "osfm_tracks_pairwise_files_write",
     "osfm_tracks_from_mve", "osfm_cameras_file_write", "osfm_cameras_file_read",
     "osfm_sparse_cloud_write", "osfm_time_measurements_write", "osfm_time_measurements_read",
+    "osfm_sift_options_default", "osfm_sift_create", "osfm_sift_destroy", "osfm_sift_extract", "osfm_sift_download",
+    "osfm_sift_debug_image", "osfm_sift_debug_keypoints",
 ]
 
 # osfm_track_feature as a numpy record (32 bytes, no padding)
@@ -196,6 +217,13 @@ if lib.osfm_version() != ABI_VERSION and os.environ.get("OSFM_ALLOW_ABI_MISMATCH
 lib.osfm_device_count.restype = C.c_int
 _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
+lib.osfm_sift_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(SiftOptions), C.POINTER(C.c_void_p)]
+lib.osfm_sift_destroy.argtypes = [C.c_void_p]
+lib.osfm_sift_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(SiftSummary)]
+lib.osfm_sift_download.argtypes = [C.c_void_p] + [C.c_void_p] * 6
+lib.osfm_sift_debug_image.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32)]
+lib.osfm_sift_debug_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
 lib.osfm_ba_debug_cholesky_solve.restype = C.c_int
 lib.osfm_ba_debug_cholesky_solve.argtypes = [C.c_int, C.c_int, _f64p, _f64p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, _f64p, _i32p, _i32p]
@@ -277,6 +305,12 @@ def library_memory() -> MemoryReport:
 def default_match_options() -> MatchOptions:
     o = MatchOptions()
     check(lib.osfm_match_options_default(C.byref(o)))
+    return o
+
+
+def default_sift_options() -> SiftOptions:
+    o = SiftOptions()
+    check(lib.osfm_sift_options_default(C.byref(o)))
     return o
 
 

@@ -91,6 +91,11 @@ class HipExhaustiveMatching:
             self._h, view, capi._ptr(sift, C.c_uint16), sift.shape[0],
             capi._ptr(surf, C.c_int16), surf.shape[0]))
 
+    def set_view_features(self, view, features):
+        """A view from features.SiftExtractor.extract: its descriptors and its normalised positions."""
+        self.set_view_float(view, features.descriptors, np.zeros((0, 64), np.float32))
+        self.set_positions(view, features.normalized)
+
     def expect_pairs(self, pairs_per_call: int):
         """The largest compute() call to come: the work arrays are sized for it at once (osfm_match_expect_pairs)."""
         capi.check(capi.lib.osfm_match_expect_pairs(self._h, C.c_int32(int(pairs_per_call))))
