@@ -886,8 +886,8 @@ OSFM_API int osfm_time_measurements_read(const char *path, double *seconds);
  * feature_set.cc:42-86), on the device.  The octave and DoG images, the candidate
  * list and the localised keypoints are equal to the reference's bytes; orientations
  * and descriptors are the same algorithm evaluated in double (DESIGN.md has the
- * measured distance).  Image files, the max_image_size halving loop of
- * bundler_features.cc:66-68 and SURF stay with the caller.
+ * measured distance).  Image files and the max_image_size halving loop of
+ * bundler_features.cc:66-68 stay with the caller; SURF is the next section.
  * ------------------------------------------------------------------------- */
 #define OSFM_SIFT_MAX_OCTAVES 16
 
@@ -900,7 +900,7 @@ typedef struct osfm_sift_options {
     float edge_ratio_threshold;       /* 10 */
     float base_blur_sigma;            /* 1.6 */
     float inherent_blur_sigma;        /* 0.5 */
-    int32_t max_keypoints;            /* 65536: more candidates or more descriptors than this is OSFM_E_CAPACITY */
+    int32_t max_keypoints;            /* 65536: more candidates than this is OSFM_E_CAPACITY (descriptors never exceed candidates) */
 } osfm_sift_options;
 OSFM_API int osfm_sift_options_default(osfm_sift_options *opts);
 
@@ -925,7 +925,8 @@ OSFM_API int osfm_sift_destroy(osfm_sift *ctx);
  *   OSFM_E_ARG       channels other than 1 or 3; a size on which the reference throws (create_octaves halves
  *                    the image once per octave, the last included, and halving needs 2 pixels a side)
  *   OSFM_E_RANGE     an image larger than the context
- *   OSFM_E_CAPACITY  more candidates or more descriptors than max_keypoints -- never a truncated result */
+ *   OSFM_E_CAPACITY  more candidates than max_keypoints -- never a truncated result; a candidate yields one
+ *                    keypoint and one descriptor at most, so neither of those can exceed it */
 OSFM_API int osfm_sift_extract(osfm_sift *ctx, const uint8_t *pixels, int width, int height, int channels,
     osfm_sift_summary *summary);
 
@@ -946,6 +947,78 @@ OSFM_API int osfm_sift_download(osfm_sift *ctx, float *descriptors, float *posit
 OSFM_API int osfm_sift_debug_image(osfm_sift *ctx, int octave, int kind, int index, float *out, int32_t *width,
     int32_t *height);
 OSFM_API int osfm_sift_debug_keypoints(osfm_sift *ctx, int after_localisation, float *out, int32_t *count);
+
+/* ---------------------------------------------------------------------------
+ * SURF feature extraction (MVE's sfm/surf.cc and FeatureSet::compute_surf,
+ * feature_set.cc:88-117), on the device.  Every stage -- the summed-area table, the
+ * 4 x 4 response maps, candidates, localised keypoints, orientations, descriptors --
+ * is held to the reference's bytes: float and double operations in its order, and
+ * the values of expf, atan2, sinf and cosf taken from the host's C library.  The one
+ * decision that cannot be pinned is the orientation window test of a sample whose
+ * atan2f lies within a few ulps of a window bound (DESIGN.md 3u counts them).
+ * Image files and the max_image_size halving loop stay with the caller.
+ * ------------------------------------------------------------------------- */
+#define OSFM_SURF_OCTAVES 4
+
+/* Surf::Options and the capacity of a context's candidate and descriptor arrays. */
+typedef struct osfm_surf_options {
+    float contrast_threshold;         /* 500 */
+    int32_t use_upright_descriptor;   /* 0 */
+    int32_t max_keypoints;            /* 65536: more candidates than this is OSFM_E_CAPACITY (descriptors never exceed candidates) */
+} osfm_surf_options;
+OSFM_API int osfm_surf_options_default(osfm_surf_options *opts);
+
+typedef struct osfm_surf_summary {
+    int32_t num_candidates, num_keypoints, num_descriptors;
+    /* descriptors with a sample tap outside the summed-area table, which the device reads as zero.  Always 0
+     * for extracted features: the descriptor's margin 15 s + 1 holds every tap of a finite keypoint inside its
+     * row.  The count is the guard of osfm_surf_debug_describe against non-finite input. */
+    int32_t num_guarded;
+    int32_t keypoints_per_octave[OSFM_SURF_OCTAVES];
+    int32_t descriptors_per_octave[OSFM_SURF_OCTAVES];
+    /* stage times from events on the context's stream; localisation, orientation and descriptors include their
+     * results' way to the host */
+    double sat_ms, response_ms, extrema_ms, localisation_ms, orientation_ms, descriptor_ms, total_ms;
+} osfm_surf_summary;
+
+typedef struct osfm_surf osfm_surf;
+
+/* A context owns the summed-area table, the response maps and the work arrays for images up to
+ * max_width x max_height (booked in osfm_library_memory as device_buffer_bytes) and serves one extraction at a
+ * time.  opts NULL: the defaults. */
+OSFM_API int osfm_surf_create(int device, int max_width, int max_height, const osfm_surf_options *opts, osfm_surf **out);
+OSFM_API int osfm_surf_destroy(osfm_surf *ctx);
+
+/* Extracts the features of an 8-bit image in host memory, row-major, channels interleaved; 3 channels are
+ * desaturated on bytes (DESATURATE_LIGHTNESS).  No size is too small: an image that fits no filter has no
+ * features, as in the reference.  On success the context holds the result until the next call and *summary (may
+ * be NULL) is filled.  Errors, none of which writes *summary or leaves a result behind:
+ *   OSFM_E_ARG       channels other than 1 or 3
+ *   OSFM_E_RANGE     an image larger than the context
+ *   OSFM_E_CAPACITY  more candidates than max_keypoints -- never a truncated result; a candidate yields one
+ *                    keypoint and one descriptor at most, so neither of those can exceed it */
+OSFM_API int osfm_surf_extract(osfm_surf *ctx, const uint8_t *pixels, int width, int height, int channels,
+    osfm_surf_summary *summary);
+
+/* The result of the last extraction in FeatureSet's order: by scale descending, descriptors of equal scale (SURF
+ * has nine scales) in the order the detector generated them (the reference's std::sort leaves those unordered).
+ * Every output is caller-allocated for num_descriptors rows and may be NULL.
+ *   descriptors [n][64], positions [n][2], scale [n], orientation [n] (radians in [-pi, pi]), colors [n][3] and
+ *   normalized_positions [n][2] as osfm_sift_download computes them */
+OSFM_API int osfm_surf_download(osfm_surf *ctx, float *descriptors, float *positions, float *scale, float *orientation,
+    uint8_t *colors, float *normalized_positions);
+
+/* Test hooks.  osfm_surf_debug_image: response map `sample` (0..3) of octave `octave` (0..3) of the last
+ * extraction; *width / *height (may be NULL) are always set; out (may be NULL) takes width * height floats.
+ * osfm_surf_debug_keypoints: rows (octave, sample, x, y) of the candidates (after_localisation 0) or of the
+ * localised keypoints (1), in the detector's order; *count (may be NULL) is always set, out may be NULL.
+ * osfm_surf_debug_describe: Surf::descriptor_computation for one hand-placed descriptor on the last image's
+ * summed-area table, scale in [1, 65) (else OSFM_E_ARG); *status 0: rejected (out is zero), 1: ok, 2: ok with taps
+ * outside the table read as zero, which only non-finite x, y or orientation can bring about. */
+OSFM_API int osfm_surf_debug_image(osfm_surf *ctx, int octave, int sample, float *out, int32_t *width, int32_t *height);
+OSFM_API int osfm_surf_debug_keypoints(osfm_surf *ctx, int after_localisation, float *out, int32_t *count);
+OSFM_API int osfm_surf_debug_describe(osfm_surf *ctx, float x, float y, float scale, float orientation, int upright,
+    float *out, int32_t *status);
 
 #ifdef __cplusplus
 }

@@ -162,6 +162,24 @@ class SiftSummary(C.Structure):
                                           "descriptor_ms", "total_ms")]
 
 
+SURF_OCTAVES = 4
+
+
+class SurfOptions(C.Structure):
+    """osfm_surf_options"""
+    _fields_ = [("contrast_threshold", C.c_float), ("use_upright_descriptor", C.c_int32), ("max_keypoints", C.c_int32)]
+
+
+class SurfSummary(C.Structure):
+    """osfm_surf_summary"""
+    _fields_ = [("num_candidates", C.c_int32), ("num_keypoints", C.c_int32), ("num_descriptors", C.c_int32),
+                ("num_guarded", C.c_int32),
+                ("keypoints_per_octave", C.c_int32 * SURF_OCTAVES),
+                ("descriptors_per_octave", C.c_int32 * SURF_OCTAVES)] + \
+               [(n, C.c_double) for n in ("sat_ms", "response_ms", "extrema_ms", "localisation_ms", "orientation_ms",
+                                          "descriptor_ms", "total_ms")]
+
+
 class BaLinCapture(C.Structure):
     """osfm_ba_lin_capture (test hook osfm_ba_debug_linearization)."""
     ARRAYS = ("scale_c", "diag_c", "S", "rhs", "scale_p", "diag_p", "vinv", "ge", "y_c", "cand_cams", "cand_points")
@@ -201,6 +219,8 @@ EXPORTS = [
     "osfm_sparse_cloud_write", "osfm_time_measurements_write", "osfm_time_measurements_read",
     "osfm_sift_options_default", "osfm_sift_create", "osfm_sift_destroy", "osfm_sift_extract", "osfm_sift_download",
     "osfm_sift_debug_image", "osfm_sift_debug_keypoints",
+    "osfm_surf_options_default", "osfm_surf_create", "osfm_surf_destroy", "osfm_surf_extract", "osfm_surf_download",
+    "osfm_surf_debug_image", "osfm_surf_debug_keypoints", "osfm_surf_debug_describe",
 ]
 
 # osfm_track_feature as a numpy record (32 bytes, no padding)
@@ -224,6 +244,14 @@ lib.osfm_sift_download.argtypes = [C.c_void_p] + [C.c_void_p] * 6
 lib.osfm_sift_debug_image.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32)]
 lib.osfm_sift_debug_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
+lib.osfm_surf_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(SurfOptions), C.POINTER(C.c_void_p)]
+lib.osfm_surf_destroy.argtypes = [C.c_void_p]
+lib.osfm_surf_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(SurfSummary)]
+lib.osfm_surf_download.argtypes = [C.c_void_p] + [C.c_void_p] * 6
+lib.osfm_surf_debug_image.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+lib.osfm_surf_debug_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
+lib.osfm_surf_debug_describe.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p,
+                                         C.POINTER(C.c_int32)]
 lib.osfm_ba_debug_cholesky_solve.restype = C.c_int
 lib.osfm_ba_debug_cholesky_solve.argtypes = [C.c_int, C.c_int, _f64p, _f64p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, _f64p, _i32p, _i32p]
@@ -311,6 +339,12 @@ def default_match_options() -> MatchOptions:
 def default_sift_options() -> SiftOptions:
     o = SiftOptions()
     check(lib.osfm_sift_options_default(C.byref(o)))
+    return o
+
+
+def default_surf_options() -> SurfOptions:
+    o = SurfOptions()
+    check(lib.osfm_surf_options_default(C.byref(o)))
     return o
 
 

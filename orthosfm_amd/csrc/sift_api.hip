@@ -5,6 +5,7 @@
 #include <memory>
 #include <numeric>
 
+#include "feature_view.h"
 #include "osfm_common.h"
 #include "sift_kernels.h"
 
@@ -113,20 +114,6 @@ int copy_image(osfm_sift *c, const float *src, int w, int h, float *out)
     OSFM_HIP_CHECK(hipMemcpyAsync(out, src, (size_t)w * h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
     return OSFM_OK;
-}
-
-// Image<unsigned char>::linear_at with interpolate<unsigned char>'s + 0.5f truncation
-void linear_at(const uint8_t *img, int w, int h, int ch, float x, float y, uint8_t *px)
-{
-    x = std::max(0.0f, std::min((float)(w - 1), x));
-    y = std::max(0.0f, std::min((float)(h - 1), y));
-    const int fx = (int)x, fy = (int)y;
-    const int fx1 = std::min(fx + 1, w - 1), fy1 = std::min(fy + 1, h - 1);
-    const float w1 = x - (float)fx, w0 = 1.0f - w1, w3 = y - (float)fy, w2 = 1.0f - w3;
-    const size_t rs = (size_t)w * ch, r1 = fy * rs, r2 = fy1 * rs, c1 = (size_t)fx * ch, c2 = (size_t)fx1 * ch;
-    for (int cc = 0; cc < ch; ++cc)
-        px[cc] = (uint8_t)((float)img[r1 + c1 + cc] * (w0 * w2) + (float)img[r1 + c2 + cc] * (w1 * w2)
-            + (float)img[r2 + c1 + cc] * (w0 * w3) + (float)img[r2 + c2 + cc] * (w1 * w3) + 0.5f);
 }
 
 int extract(osfm_sift *c, const uint8_t *pixels, int width, int height, int channels, osfm_sift_summary *sum_out)
@@ -305,7 +292,6 @@ int extract(osfm_sift *c, const uint8_t *pixels, int width, int height, int chan
     for (const Keypoint &k : h_kps) sum.keypoints_per_octave[(int)k.octave - o.min_octave]++;
     c->positions.resize((size_t)n_desc * 2); c->normalized.resize((size_t)n_desc * 2);
     c->scale.resize((size_t)n_desc); c->orientation.resize((size_t)n_desc); c->colors.resize((size_t)n_desc * 3);
-    const float fw = (float)width, fh = (float)height, fnorm = std::max(fw, fh);
     for (int j = 0; j < n_desc; ++j) {
         const Keypoint &k = h_kps[(size_t)jobs[(size_t)j].keypoint];
         sum.descriptors_per_octave[(int)k.octave - o.min_octave]++;
@@ -314,15 +300,9 @@ int extract(osfm_sift *c, const uint8_t *pixels, int width, int height, int chan
         c->positions[2 * (size_t)j] = x; c->positions[2 * (size_t)j + 1] = y;
         c->scale[(size_t)j] = abs_scale[(size_t)jobs[(size_t)j].keypoint];
         c->orientation[(size_t)j] = jobs[(size_t)j].orientation;
-        uint8_t px[3] = {0, 0, 0};
-        linear_at(pixels, width, height, channels, x, y, px);
-        for (int k3 = 0; k3 < 3; ++k3) c->colors[3 * (size_t)j + k3] = channels == 3 ? px[k3] : px[0];
-        c->normalized[2 * (size_t)j] = (x + 0.5f - fw * 0.5f) / fnorm;
-        c->normalized[2 * (size_t)j + 1] = (y + 0.5f - fh * 0.5f) / fnorm;
+        feature_view_row(pixels, width, height, channels, x, y, &c->colors[3 * (size_t)j], &c->normalized[2 * (size_t)j]);
     }
-    c->order.resize((size_t)n_desc);
-    std::iota(c->order.begin(), c->order.end(), 0);
-    std::stable_sort(c->order.begin(), c->order.end(), [c](int32_t a, int32_t b) { return c->scale[(size_t)a] > c->scale[(size_t)b]; });
+    feature_view_order(c->scale, &c->order);
     float ms[5] = {};
     for (int i = 0; i < 5; ++i) OSFM_HIP_CHECK(hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
     sum.scale_space_ms = ms[0]; sum.extrema_ms = ms[1]; sum.localisation_ms = ms[2]; sum.orientation_ms = ms[3];

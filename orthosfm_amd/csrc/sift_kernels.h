@@ -63,6 +63,24 @@ void launch_orientation(hipStream_t s, PyramidView pyr, const Keypoint *kps, con
 void launch_descriptor(hipStream_t s, PyramidView pyr, const Keypoint *kps, const float *sigma, const DescriptorJob *jobs,
     int n, float *out);
 
+// Rank of this thread among the flagged threads of its workgroup (kBlock threads), in thread order, and their
+// number: the ranked write of the count / scan / write scheme, shared with the SURF kernels.
+__device__ inline int block_rank(bool flag, int *block_total)
+{
+    __shared__ int wave_count[kBlock / 64];
+    const unsigned long long m = __ballot(flag);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_count[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int i = 0; i < kBlock / 64; ++i) {
+        if (i < wave) before += wave_count[i];
+        total += wave_count[i];
+    }
+    *block_total = total;
+    return before + __popcll(m & ((1ull << lane) - 1ull));
+}
+
 inline int extrema_blocks(int w, int h)
 {
     if (w < 3 || h < 3) return 0;

@@ -123,23 +123,6 @@ __global__ __launch_bounds__(kBlock) void blur_cols_kernel(const float *in, floa
 
 // ----------------------------------------------------------------------------- ordered compaction
 
-// Rank of this thread among the flagged threads of its workgroup, in thread order, and their number.
-__device__ inline int block_rank(bool flag, int *block_total)
-{
-    __shared__ int wave_count[kBlock / 64];
-    const unsigned long long m = __ballot(flag);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wave_count[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int i = 0; i < kBlock / 64; ++i) {
-        if (i < wave) before += wave_count[i];
-        total += wave_count[i];
-    }
-    *block_total = total;
-    return before + __popcll(m & ((1ull << lane) - 1ull));
-}
-
 // Strict 26-neighbour extrema of the interior pixels, one thread per pixel in (y, x) order.
 template <bool WRITE>
 __global__ __launch_bounds__(kBlock) void extrema_kernel(const float *d0, const float *d1, const float *d2, int w, int h,

@@ -1,0 +1,434 @@
+// C ABI of the SURF extraction (include/osfm_hip.h, "SURF feature extraction"): owns the summed-area table and
+// the response maps, runs the stages of surf_kernels.hip in the reference's order, and keeps
+// FeatureSet::compute_surf's view of the result.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+
+#include "feature_view.h"
+#include "osfm_common.h"
+#include "surf_kernels.h"
+
+using namespace osfm;
+using namespace osfm::surf;
+
+struct osfm_surf {
+    int device = 0, max_w = 0, max_h = 0;
+    osfm_surf_options opts{};
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[7] = {};
+    DeviceBuffer pixels, sat, maps, cand, moved, kps, keep, counts, total, table, weights, ori_jobs, ori_out, desc_jobs, desc,
+        status;
+    size_t map_floats = 0;
+    int max_blocks = 0;
+    // the last extraction
+    bool have = false;
+    int width = 0, height = 0;
+    MapsView view{};
+    int n_cand = 0, n_kp = 0, n_desc = 0;
+    std::vector<int32_t> rows;             // generation row j is descriptor job rows[j]
+    std::vector<float> positions, scale, orientation, normalized;   // in generation order
+    std::vector<uint8_t> colors;
+    std::vector<int32_t> order;            // FeatureSet's order: row i is generation row order[i]
+    ~osfm_surf()
+    {
+        for (auto &e : ev) event_destroy(e);
+        stream_destroy(stream);
+    }
+};
+
+namespace {
+
+// Filter sizes (a third of the kernel's side): fs = 2^(o + 1) (k + 1) + 1
+int filter_size(int o, int k) { return (2 << o) * (k + 1) + 1; }
+
+// The response maps of a w x h image: per octave ceil(w / 2^o) x ceil(h / 2^o), four planes.
+size_t plan_maps(int w, int h, MapsView *mv, int *blocks)
+{
+    size_t n = 0;
+    int total_blocks = 0;
+    for (int o = 0; o < kOctaves; ++o) {
+        if (mv) { mv->ow[o] = w; mv->oh[o] = h; mv->offset[o] = n; }
+        n += (size_t)kSamples * w * h;
+        total_blocks += 2 * extrema_blocks(w, h);
+        w = (w + 1) >> 1; h = (h + 1) >> 1;
+    }
+    if (blocks) *blocks = total_blocks;
+    return n;
+}
+
+// Surf::descriptor_assignment's scale of a keypoint, by the reference's float expression.
+float keypoint_scale(const Keypoint &k)
+{
+    const int sample = (int)(k.sample + 0.5f);
+    return 3 * filter_size((int)k.octave, sample) * 1.2f / 9.0f;
+}
+
+int describe(osfm_surf *c, const std::vector<DescJob> &jobs, std::vector<int32_t> *status)
+{
+    const size_t n = jobs.size();
+    status->assign(n, 0);
+    if (!n) return OSFM_OK;
+    hipStream_t s = c->stream;
+    OSFM_HIP_CHECK(hipMemcpyAsync(c->desc_jobs.ptr, jobs.data(), n * sizeof(DescJob), hipMemcpyHostToDevice, s));
+    launch_descriptor(s, c->sat.as<Sat>(), c->width, c->height, c->weights.as<float>(), c->desc_jobs.as<DescJob>(), (int)n,
+        c->desc.as<float>(), c->status.as<int32_t>());
+    OSFM_HIP_CHECK(hipGetLastError());
+    OSFM_HIP_CHECK(hipMemcpyAsync(status->data(), c->status.ptr, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    OSFM_HIP_CHECK(hipStreamSynchronize(s));
+    return OSFM_OK;
+}
+
+int extract(osfm_surf *c, const uint8_t *pixels, int width, int height, int channels, osfm_surf_summary *sum_out)
+{
+    const osfm_surf_options &o = c->opts;
+    hipStream_t s = c->stream;
+    MapsView mv{};
+    int total_blocks = 0;
+    if (plan_maps(width, height, &mv, &total_blocks) > c->map_floats || total_blocks > c->max_blocks) {
+        set_error("osfm_surf_extract: internal: the maps of %d x %d exceed the context's", width, height);
+        return OSFM_E_STATE;
+    }
+    mv.maps = c->maps.as<float>();
+    Sat *sat = c->sat.as<Sat>();
+
+    // ---- summed-area table
+    OSFM_HIP_CHECK(hipEventRecord(c->ev[0], s));
+    OSFM_HIP_CHECK(hipMemcpyAsync(c->pixels.ptr, pixels, (size_t)width * height * channels, hipMemcpyHostToDevice, s));
+    launch_sat(s, c->pixels.as<uint8_t>(), width, height, channels, sat);
+
+    // ---- response maps
+    OSFM_HIP_CHECK(hipEventRecord(c->ev[1], s));
+    for (int oi = 0; oi < kOctaves; ++oi) {
+        OctaveFilters f;
+        for (int k = 0; k < kSamples; ++k) {
+            const int fs = filter_size(oi, k);
+            f.fs[k] = fs;
+            f.inv_karea[k] = 1.0 / (fs * (2 * fs - 1));
+        }
+        launch_response(s, sat, width, height, oi, f, mv.maps + mv.offset[oi], mv.ow[oi], mv.oh[oi]);
+    }
+    OSFM_HIP_CHECK(hipGetLastError());
+
+    // ---- extrema: count per workgroup, scan, write in (octave, sample, y, x) order
+    OSFM_HIP_CHECK(hipEventRecord(c->ev[2], s));
+    int32_t *counts = c->counts.as<int32_t>(), *total = c->total.as<int32_t>();
+    Keypoint *cand = c->cand.as<Keypoint>();
+    for (int pass = 0; pass < 2; ++pass) {
+        int base = 0;
+        for (int oi = 0; oi < kOctaves; ++oi) {
+            const size_t plane = (size_t)mv.ow[oi] * mv.oh[oi];
+            for (int si = 1; si < 3; ++si) {
+                const float *m1 = mv.maps + mv.offset[oi] + (size_t)si * plane;
+                surf::launch_extrema(s, m1 - plane, m1, m1 + plane, mv.ow[oi], mv.oh[oi], base, counts, pass ? counts : nullptr, cand,
+                    o.max_keypoints, (float)oi, (float)si);
+                base += extrema_blocks(mv.ow[oi], mv.oh[oi]);
+            }
+        }
+        if (!pass) sift::launch_scan(s, counts, base, total);
+    }
+    int32_t n_cand = 0;
+    OSFM_HIP_CHECK(hipMemcpyAsync(&n_cand, total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    OSFM_HIP_CHECK(hipStreamSynchronize(s));
+    if (n_cand > o.max_keypoints) {
+        set_error("osfm_surf_extract: %d candidates exceed max_keypoints %d", n_cand, o.max_keypoints);
+        return OSFM_E_CAPACITY;
+    }
+
+    // ---- localisation and compaction
+    OSFM_HIP_CHECK(hipEventRecord(c->ev[3], s));
+    int32_t n_kp = 0;
+    std::vector<Keypoint> h_kps;
+    if (n_cand > 0) {
+        surf::launch_localise(s, mv, o.contrast_threshold, width, height, cand, n_cand, c->moved.as<Keypoint>(), c->keep.as<uint8_t>(),
+            counts);
+        sift::launch_scan(s, counts, (n_cand + kBlock - 1) / kBlock, total);
+        sift::launch_compact(s, c->moved.as<Keypoint>(), c->keep.as<uint8_t>(), counts, n_cand, c->kps.as<Keypoint>());
+        OSFM_HIP_CHECK(hipMemcpyAsync(&n_kp, total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        OSFM_HIP_CHECK(hipStreamSynchronize(s));
+        h_kps.resize((size_t)n_kp);
+        if (n_kp) {
+            OSFM_HIP_CHECK(hipMemcpyAsync(h_kps.data(), c->kps.ptr, (size_t)n_kp * sizeof(Keypoint), hipMemcpyDeviceToHost, s));
+            OSFM_HIP_CHECK(hipStreamSynchronize(s));
+        }
+    }
+
+    // ---- orientation: the windows on the device, atan2 / sinf / cosf of the winner from the C library
+    OSFM_HIP_CHECK(hipEventRecord(c->ev[4], s));
+    std::vector<float> kp_scale((size_t)n_kp);
+    std::vector<OriJob> ori_jobs((size_t)n_kp);
+    std::vector<OriResult> ori((size_t)n_kp);
+    for (int i = 0; i < n_kp; ++i) {
+        const Keypoint &k = h_kps[(size_t)i];
+        kp_scale[(size_t)i] = keypoint_scale(k);
+        ori_jobs[(size_t)i] = OriJob{(int)(k.x + 0.5f), (int)(k.y + 0.5f), (int)kp_scale[(size_t)i]};
+    }
+    if (n_kp) {
+        OSFM_HIP_CHECK(hipMemcpyAsync(c->ori_jobs.ptr, ori_jobs.data(), (size_t)n_kp * sizeof(OriJob), hipMemcpyHostToDevice, s));
+        launch_orientation(s, sat, width, height, c->table.as<OriTable>(), c->ori_jobs.as<OriJob>(), n_kp, c->ori_out.as<OriResult>());
+        OSFM_HIP_CHECK(hipGetLastError());
+        OSFM_HIP_CHECK(hipMemcpyAsync(ori.data(), c->ori_out.ptr, (size_t)n_kp * sizeof(OriResult), hipMemcpyDeviceToHost, s));
+        OSFM_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    std::vector<DescJob> jobs;
+    std::vector<int32_t> job_kp;
+    std::vector<float> job_ori;
+    for (int i = 0; i < n_kp; ++i) {
+        if (!ori[(size_t)i].ok) continue;
+        const Keypoint &k = h_kps[(size_t)i];
+        const float orientation = std::atan2(ori[(size_t)i].best_dy, ori[(size_t)i].best_dx);
+        DescJob j{k.x, k.y, (int)kp_scale[(size_t)i], 0.0f, 1.0f};
+        if (!o.use_upright_descriptor) {
+            j.sin_ori = std::sin(orientation);
+            j.cos_ori = std::cos(orientation);
+        }
+        jobs.push_back(j);
+        job_kp.push_back(i);
+        job_ori.push_back(orientation);
+    }
+
+    // ---- descriptors
+    OSFM_HIP_CHECK(hipEventRecord(c->ev[5], s));
+    c->width = width; c->height = height;        // describe() reads them
+    std::vector<int32_t> status;
+    OSFM_RETURN_IF(describe(c, jobs, &status));
+    OSFM_HIP_CHECK(hipEventRecord(c->ev[6], s));
+    OSFM_HIP_CHECK(hipStreamSynchronize(s));
+
+    // ---- FeatureSet::compute_surf's view: positions, colours, the order by scale
+    osfm_surf_summary sum;
+    std::memset(&sum, 0, sizeof(sum));
+    sum.num_candidates = n_cand; sum.num_keypoints = n_kp;
+    for (const Keypoint &k : h_kps) sum.keypoints_per_octave[(int)k.octave]++;
+    std::vector<int32_t> rows;
+    for (size_t j = 0; j < jobs.size(); ++j)
+        if (status[j]) rows.push_back((int32_t)j);
+    const int n_desc = (int)rows.size();     // <= n_kp <= n_cand <= max_keypoints: one per keypoint at most
+    sum.num_descriptors = n_desc;
+    c->positions.resize((size_t)n_desc * 2); c->normalized.resize((size_t)n_desc * 2);
+    c->scale.resize((size_t)n_desc); c->orientation.resize((size_t)n_desc); c->colors.resize((size_t)n_desc * 3);
+    for (int r = 0; r < n_desc; ++r) {
+        const size_t j = (size_t)rows[(size_t)r];
+        const Keypoint &k = h_kps[(size_t)job_kp[j]];
+        sum.descriptors_per_octave[(int)k.octave]++;
+        sum.num_guarded += status[j] == 2;
+        c->positions[2 * (size_t)r] = k.x; c->positions[2 * (size_t)r + 1] = k.y;
+        c->scale[(size_t)r] = kp_scale[(size_t)job_kp[j]];
+        c->orientation[(size_t)r] = job_ori[j];
+        feature_view_row(pixels, width, height, channels, k.x, k.y, &c->colors[3 * (size_t)r], &c->normalized[2 * (size_t)r]);
+    }
+    feature_view_order(c->scale, &c->order);
+    float ms[6] = {};
+    for (int i = 0; i < 6; ++i) OSFM_HIP_CHECK(hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
+    sum.sat_ms = ms[0]; sum.response_ms = ms[1]; sum.extrema_ms = ms[2]; sum.localisation_ms = ms[3]; sum.orientation_ms = ms[4];
+    sum.descriptor_ms = ms[5];
+    sum.total_ms = (double)ms[0] + ms[1] + ms[2] + ms[3] + ms[4] + ms[5];
+    c->view = mv;
+    c->n_cand = n_cand; c->n_kp = n_kp; c->n_desc = n_desc;
+    c->rows.swap(rows);
+    c->have = true;
+    if (sum_out) *sum_out = sum;
+    return OSFM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int osfm_surf_options_default(osfm_surf_options *o)
+{
+    if (!o) { set_error("osfm_surf_options_default: null argument"); return OSFM_E_ARG; }
+    o->contrast_threshold = 500.0f;
+    o->use_upright_descriptor = 0;
+    o->max_keypoints = 65536;
+    return OSFM_OK;
+}
+
+int osfm_surf_create(int device, int max_width, int max_height, const osfm_surf_options *opts, osfm_surf **out)
+{
+    if (!out) { set_error("osfm_surf_create: null argument"); return OSFM_E_ARG; }
+    *out = nullptr;
+    osfm_surf_options o;
+    (void)osfm_surf_options_default(&o);
+    if (opts) o = *opts;
+    if (max_width < 1 || max_height < 1 || max_width > 16384 || max_height > 16384) {
+        set_error("osfm_surf_create: image size %d x %d outside 1..16384", max_width, max_height);
+        return OSFM_E_ARG;
+    }
+    if (o.max_keypoints < 1) { set_error("osfm_surf_create: invalid options (max_keypoints >= 1)"); return OSFM_E_ARG; }
+    int ndev = 0;
+    OSFM_HIP_CHECK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) { set_error("osfm_surf_create: device %d of %d", device, ndev); return OSFM_E_ARG; }
+    OSFM_HIP_CHECK(hipSetDevice(device));
+    std::unique_ptr<osfm_surf> c(new osfm_surf);
+    c->device = device; c->max_w = max_width; c->max_h = max_height; c->opts = o;
+    c->map_floats = plan_maps(max_width, max_height, nullptr, &c->max_blocks);
+    const size_t K = (size_t)o.max_keypoints;
+    c->max_blocks = std::max(c->max_blocks, (int)((K + kBlock - 1) / kBlock)) + 1;
+    OSFM_RETURN_IF(c->pixels.reserve((size_t)max_width * max_height * 3));
+    OSFM_RETURN_IF(c->sat.reserve((size_t)max_width * max_height * sizeof(Sat)));
+    OSFM_RETURN_IF(c->maps.reserve(c->map_floats * sizeof(float)));
+    OSFM_RETURN_IF(c->cand.reserve(K * sizeof(Keypoint)));
+    OSFM_RETURN_IF(c->moved.reserve(K * sizeof(Keypoint)));
+    OSFM_RETURN_IF(c->kps.reserve(K * sizeof(Keypoint)));
+    OSFM_RETURN_IF(c->keep.reserve(K));
+    OSFM_RETURN_IF(c->counts.reserve((size_t)c->max_blocks * sizeof(int32_t)));
+    OSFM_RETURN_IF(c->total.reserve(sizeof(int32_t)));
+    OSFM_RETURN_IF(c->table.reserve(sizeof(OriTable)));
+    OSFM_RETURN_IF(c->weights.reserve(400 * sizeof(float)));
+    OSFM_RETURN_IF(c->ori_jobs.reserve(K * sizeof(OriJob)));
+    OSFM_RETURN_IF(c->ori_out.reserve(K * sizeof(OriResult)));
+    // one slot more than descriptors: osfm_surf_debug_describe's
+    OSFM_RETURN_IF(c->desc_jobs.reserve((K + 1) * sizeof(DescJob)));
+    OSFM_RETURN_IF(c->desc.reserve((K + 1) * 64 * sizeof(float)));
+    OSFM_RETURN_IF(c->status.reserve((K + 1) * sizeof(int32_t)));
+    OSFM_HIP_CHECK(stream_create(&c->stream));
+    for (auto &e : c->ev) OSFM_HIP_CHECK(event_create(&e, true));
+    // the orientation window's Gaussian (sigma 2.5) as the reference spells it: six significant digits
+    OriTable table;
+    int index = 0;
+    for (int ry = -5; ry <= 5; ++ry)
+        for (int rx = -5; rx <= 5; ++rx) {
+            if (rx * rx + ry * ry >= 36) continue;
+            char text[32];
+            std::snprintf(text, sizeof(text), "%.6g", std::exp(-(double)(rx * rx + ry * ry) / 12.5));
+            table.gauss[index] = (float)std::strtod(text, nullptr);
+            table.rx[index] = (signed char)rx;
+            table.ry[index] = (signed char)ry;
+            ++index;
+        }
+    // the descriptor's Gaussian (sigma 3.3 s) by the reference's float expression with the C library's expf
+    float weights[400];
+    const float six = 2.0f * 3.3f, sq = six * six;
+    for (int y = -10; y < 10; ++y)
+        for (int x = -10; x < 10; ++x) weights[(y + 10) * 20 + (x + 10)] = std::exp(-(float)(x * x + y * y) / sq);
+    OSFM_HIP_CHECK(hipMemcpyAsync(c->table.ptr, &table, sizeof(table), hipMemcpyHostToDevice, c->stream));
+    OSFM_HIP_CHECK(hipMemcpyAsync(c->weights.ptr, weights, sizeof(weights), hipMemcpyHostToDevice, c->stream));
+    OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    *out = c.release();
+    return OSFM_OK;
+}
+
+int osfm_surf_destroy(osfm_surf *c)
+{
+    if (!c) return OSFM_OK;
+    (void)hipSetDevice(c->device);
+    delete c;
+    return OSFM_OK;
+}
+
+int osfm_surf_extract(osfm_surf *c, const uint8_t *pixels, int width, int height, int channels, osfm_surf_summary *summary)
+{
+    if (!c || !pixels) { set_error("osfm_surf_extract: null argument"); return OSFM_E_ARG; }
+    c->have = false;          // whatever comes of this call, the previous result is gone
+    if (channels != 1 && channels != 3) {
+        set_error("osfm_surf_extract: %d channels: a grey (1) or colour (3) image is expected", channels);
+        return OSFM_E_ARG;
+    }
+    if (width < 1 || height < 1) { set_error("osfm_surf_extract: image size %d x %d", width, height); return OSFM_E_ARG; }
+    if (width > c->max_w || height > c->max_h) {
+        set_error("osfm_surf_extract: a %d x %d image exceeds the context's %d x %d", width, height, c->max_w, c->max_h);
+        return OSFM_E_RANGE;
+    }
+    OSFM_HIP_CHECK(hipSetDevice(c->device));
+    const int rc = extract(c, pixels, width, height, channels, summary);
+    if (rc != OSFM_OK) (void)hipStreamSynchronize(c->stream);   // nothing of a failed call may still run
+    return rc;
+}
+
+int osfm_surf_download(osfm_surf *c, float *descriptors, float *positions, float *scale, float *orientation, uint8_t *colors,
+    float *normalized_positions)
+{
+    if (!c) { set_error("osfm_surf_download: null argument"); return OSFM_E_ARG; }
+    if (!c->have) { set_error("osfm_surf_download: no extraction to download"); return OSFM_E_STATE; }
+    OSFM_HIP_CHECK(hipSetDevice(c->device));
+    const size_t n = (size_t)c->n_desc;
+    if (descriptors && n) {
+        const size_t jobs = (size_t)c->rows.back() + 1;
+        std::vector<float> gen(jobs * 64);
+        OSFM_HIP_CHECK(hipMemcpyAsync(gen.data(), c->desc.ptr, gen.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < n; ++i)
+            std::memcpy(descriptors + i * 64, gen.data() + (size_t)c->rows[(size_t)c->order[i]] * 64, 64 * sizeof(float));
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const size_t g = (size_t)c->order[i];
+        if (positions) { positions[2 * i] = c->positions[2 * g]; positions[2 * i + 1] = c->positions[2 * g + 1]; }
+        if (scale) scale[i] = c->scale[g];
+        if (orientation) orientation[i] = c->orientation[g];
+        if (colors) std::memcpy(colors + 3 * i, c->colors.data() + 3 * g, 3);
+        if (normalized_positions) {
+            normalized_positions[2 * i] = c->normalized[2 * g];
+            normalized_positions[2 * i + 1] = c->normalized[2 * g + 1];
+        }
+    }
+    return OSFM_OK;
+}
+
+int osfm_surf_debug_image(osfm_surf *c, int octave, int sample, float *out, int32_t *width, int32_t *height)
+{
+    if (!c) { set_error("osfm_surf_debug_image: null argument"); return OSFM_E_ARG; }
+    if (!c->have) { set_error("osfm_surf_debug_image: no extraction"); return OSFM_E_STATE; }
+    if (octave < 0 || octave >= kOctaves || sample < 0 || sample >= kSamples) {
+        set_error("osfm_surf_debug_image: octave %d sample %d out of range", octave, sample);
+        return OSFM_E_ARG;
+    }
+    const int w = c->view.ow[octave], h = c->view.oh[octave];
+    if (width) *width = w;
+    if (height) *height = h;
+    if (!out) return OSFM_OK;
+    OSFM_HIP_CHECK(hipSetDevice(c->device));
+    const size_t plane = (size_t)w * h;
+    OSFM_HIP_CHECK(hipMemcpyAsync(out, c->view.maps + c->view.offset[octave] + (size_t)sample * plane, plane * sizeof(float),
+        hipMemcpyDeviceToHost, c->stream));
+    OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return OSFM_OK;
+}
+
+int osfm_surf_debug_keypoints(osfm_surf *c, int after_localisation, float *out, int32_t *count)
+{
+    if (!c) { set_error("osfm_surf_debug_keypoints: null argument"); return OSFM_E_ARG; }
+    if (!c->have) { set_error("osfm_surf_debug_keypoints: no extraction"); return OSFM_E_STATE; }
+    const int n = after_localisation ? c->n_kp : c->n_cand;
+    if (count) *count = n;
+    if (!out || !n) return OSFM_OK;
+    OSFM_HIP_CHECK(hipSetDevice(c->device));
+    OSFM_HIP_CHECK(hipMemcpyAsync(out, after_localisation ? c->kps.ptr : c->cand.ptr, (size_t)n * sizeof(Keypoint),
+        hipMemcpyDeviceToHost, c->stream));
+    OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return OSFM_OK;
+}
+
+int osfm_surf_debug_describe(osfm_surf *c, float x, float y, float scale, float orientation, int upright, float *out,
+    int32_t *status)
+{
+    if (!c || !out || !status) { set_error("osfm_surf_debug_describe: null argument"); return OSFM_E_ARG; }
+    if (!c->have) { set_error("osfm_surf_debug_describe: no extraction"); return OSFM_E_STATE; }
+    // the largest scale of the detector is 26.0; the bound keeps the kernel's int products of the scale small
+    if (!(scale >= 1.0f && scale < 65.0f)) {
+        set_error("osfm_surf_debug_describe: scale %g outside [1, 65)", (double)scale);
+        return OSFM_E_ARG;
+    }
+    OSFM_HIP_CHECK(hipSetDevice(c->device));
+    DescJob j{x, y, (int)scale, 0.0f, 1.0f};
+    if (!upright) {
+        j.sin_ori = std::sin(orientation);
+        j.cos_ori = std::cos(orientation);
+    }
+    // the hook borrows the slot behind the last extraction's descriptors, so that a download still returns those
+    const size_t slot = c->rows.empty() ? 0 : (size_t)c->rows.back() + 1;
+    hipStream_t s = c->stream;
+    DescJob *d_job = c->desc_jobs.as<DescJob>() + slot;
+    OSFM_HIP_CHECK(hipMemcpyAsync(d_job, &j, sizeof(j), hipMemcpyHostToDevice, s));
+    launch_descriptor(s, c->sat.as<Sat>(), c->width, c->height, c->weights.as<float>(), d_job, 1, c->desc.as<float>() + slot * 64,
+        c->status.as<int32_t>() + slot);
+    OSFM_HIP_CHECK(hipGetLastError());
+    OSFM_HIP_CHECK(hipMemcpyAsync(out, c->desc.as<float>() + slot * 64, 64 * sizeof(float), hipMemcpyDeviceToHost, s));
+    OSFM_HIP_CHECK(hipMemcpyAsync(status, c->status.as<int32_t>() + slot, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    OSFM_HIP_CHECK(hipStreamSynchronize(s));
+    return OSFM_OK;
+}
+
+}  // extern "C"

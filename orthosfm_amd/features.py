@@ -1,11 +1,14 @@
-"""SIFT feature extraction on the device (include/osfm_hip.h, "SIFT feature extraction").
+"""SIFT and SURF feature extraction on the device (include/osfm_hip.h, "SIFT feature extraction" and "SURF feature
+extraction").
 
-    ex = SiftExtractor(device=0, max_width=2048, max_height=2048)
-    f = ex.extract(image)                 # uint8 [h, w] or [h, w, 3]
-    matcher.set_view_features(0, f)
+    ex = FeatureSetExtractor(device=0, max_width=2048, max_height=2048)
+    fs = ex.extract(image)                # uint8 [h, w] or [h, w, 3]; fs.sift, fs.surf
+    matcher.set_view_features(0, fs)
 
-The result is FeatureSet::compute_sift's: sorted by scale, descending.  Reading image files and the halving of
-images beyond a maximum size stay with the caller.
+    f = SiftExtractor(0, 2048, 2048).extract(image)      # one detector alone; SurfExtractor likewise
+
+A FeatureSet is the reference's with FEATURE_ALL: SIFT rows, then SURF rows, each sorted by scale, descending.
+Reading image files and the halving of images beyond a maximum size stay with the caller.
 """
 from __future__ import annotations
 
@@ -19,11 +22,11 @@ from . import capi
 
 @dataclass
 class Features:
-    descriptors: np.ndarray     # float32 [n, 128]
+    descriptors: np.ndarray     # float32 [n, 128] (SIFT) or [n, 64] (SURF)
     positions: np.ndarray       # float32 [n, 2], x, y in pixels of the input image
     normalized: np.ndarray      # float32 [n, 2], FeatureSet::normalize_feature_positions
     scale: np.ndarray           # float32 [n]
-    orientation: np.ndarray     # float32 [n], radians in [0, 2 pi]
+    orientation: np.ndarray     # float32 [n], radians: SIFT in [0, 2 pi], SURF in [-pi, pi]
     colors: np.ndarray          # uint8 [n, 3]
 
     def __len__(self):
@@ -101,3 +104,131 @@ class SiftExtractor:
         out = np.zeros((n.value, 4), np.float32)
         capi.check(capi.lib.osfm_sift_debug_keypoints(self._h, int(after_localisation), out.ctypes.data, None))
         return out
+
+
+def _image_arg(who, image):
+    image = np.asarray(image)
+    if image.dtype != np.uint8 or image.ndim not in (2, 3):
+        raise TypeError(f"{who}: an uint8 image [h, w] or [h, w, channels] is expected")
+    image = np.ascontiguousarray(image)
+    return image, 1 if image.ndim == 2 else image.shape[2]
+
+
+class SurfExtractor:
+    """One context (osfm_surf): the summed-area table, the response maps and work arrays for images up to
+    max_width x max_height.  The keyword options are the fields of osfm_surf_options (Surf::Options and
+    max_keypoints)."""
+
+    def __init__(self, device: int = 0, max_width: int = 2048, max_height: int = 2048, **opts):
+        o = capi.default_surf_options()
+        for k, v in opts.items():
+            if not hasattr(o, k):
+                raise TypeError(f"SurfExtractor: unknown option {k!r}")
+            setattr(o, k, v)
+        self.options = o
+        self.summary = None
+        self._h = C.c_void_p()
+        capi.check(capi.lib.osfm_surf_create(device, int(max_width), int(max_height), C.byref(o), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            capi.check(capi.lib.osfm_surf_destroy(self._h))
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def run(self, image) -> capi.SurfSummary:
+        """osfm_surf_extract alone: the summary (counts and stage times); the result stays in the context."""
+        image, channels = _image_arg("SurfExtractor", image)
+        s = capi.SurfSummary()
+        capi.check(capi.lib.osfm_surf_extract(self._h, image.ctypes.data, image.shape[1], image.shape[0], channels, C.byref(s)))
+        self.summary = s
+        return s
+
+    def download(self) -> Features:
+        """osfm_surf_download of the last run()."""
+        n = self.summary.num_descriptors
+        f = Features(np.zeros((n, 64), np.float32), np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32),
+                     np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.uint8))
+        capi.check(capi.lib.osfm_surf_download(self._h, f.descriptors.ctypes.data, f.positions.ctypes.data, f.scale.ctypes.data,
+                                               f.orientation.ctypes.data, f.colors.ctypes.data, f.normalized.ctypes.data))
+        return f
+
+    def extract(self, image) -> Features:
+        self.run(image)
+        return self.download()
+
+    # --- test hooks ---------------------------------------------------------------------------------------------
+    def debug_image(self, octave: int, sample: int) -> np.ndarray:
+        w, h = C.c_int32(), C.c_int32()
+        capi.check(capi.lib.osfm_surf_debug_image(self._h, octave, sample, None, C.byref(w), C.byref(h)))
+        out = np.zeros((h.value, w.value), np.float32)
+        capi.check(capi.lib.osfm_surf_debug_image(self._h, octave, sample, out.ctypes.data, None, None))
+        return out
+
+    def debug_keypoints(self, after_localisation: bool) -> np.ndarray:
+        n = C.c_int32()
+        capi.check(capi.lib.osfm_surf_debug_keypoints(self._h, int(after_localisation), None, C.byref(n)))
+        out = np.zeros((n.value, 4), np.float32)
+        capi.check(capi.lib.osfm_surf_debug_keypoints(self._h, int(after_localisation), out.ctypes.data, None))
+        return out
+
+    def debug_describe(self, x, y, scale, orientation, upright=False):
+        """(descriptor [64], status) of one hand-placed descriptor on the last image: status 0 rejected, 1 ok,
+        2 ok with taps outside the summed-area table read as zero (non-finite input only).  scale in [1, 65)."""
+        out, status = np.zeros(64, np.float32), C.c_int32()
+        capi.check(capi.lib.osfm_surf_debug_describe(self._h, float(x), float(y), float(scale), float(orientation), int(upright),
+                                                     out.ctypes.data, C.byref(status)))
+        return out, status.value
+
+
+@dataclass
+class FeatureSet:
+    """FeatureSet::compute_features with FEATURE_ALL: both detectors' descriptors, and positions and colours of
+    the SIFT rows followed by the SURF rows."""
+    sift: Features
+    surf: Features
+    positions: np.ndarray       # float32 [n_sift + n_surf, 2]
+    normalized: np.ndarray      # float32 [n_sift + n_surf, 2]
+    colors: np.ndarray          # uint8 [n_sift + n_surf, 3]
+
+    def __len__(self):
+        return len(self.sift) + len(self.surf)
+
+
+class FeatureSetExtractor:
+    """A SIFT and a SURF context for images up to max_width x max_height; `sift` and `surf` are dictionaries of
+    their options."""
+
+    def __init__(self, device: int = 0, max_width: int = 2048, max_height: int = 2048, sift=None, surf=None):
+        self.sift = SiftExtractor(device, max_width, max_height, **(sift or {}))
+        try:
+            self.surf = SurfExtractor(device, max_width, max_height, **(surf or {}))
+        except Exception:
+            self.sift.close()
+            raise
+
+    def close(self):
+        self.sift.close()
+        self.surf.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def extract(self, image) -> FeatureSet:
+        a, b = self.sift.extract(image), self.surf.extract(image)
+        return FeatureSet(a, b, np.concatenate([a.positions, b.positions]), np.concatenate([a.normalized, b.normalized]),
+                          np.concatenate([a.colors, b.colors]))

@@ -92,8 +92,12 @@ class HipExhaustiveMatching:
             capi._ptr(surf, C.c_int16), surf.shape[0]))
 
     def set_view_features(self, view, features):
-        """A view from features.SiftExtractor.extract: its descriptors and its normalised positions."""
-        self.set_view_float(view, features.descriptors, np.zeros((0, 64), np.float32))
+        """A view from features.SiftExtractor.extract (its descriptors and its normalised positions) or from
+        features.FeatureSetExtractor.extract (SIFT and SURF descriptors, and the positions of both, SIFT first)."""
+        if hasattr(features, "sift") and hasattr(features, "surf"):
+            self.set_view_float(view, features.sift.descriptors, features.surf.descriptors)
+        else:
+            self.set_view_float(view, features.descriptors, np.zeros((0, 64), np.float32))
         self.set_positions(view, features.normalized)
 
     def expect_pairs(self, pairs_per_call: int):
