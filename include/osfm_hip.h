@@ -40,7 +40,8 @@ OSFM_API const char *osfm_last_error(void);
  * adapters (the headers under orthosfm_amd/host) and the Python mirror compare this with their own OSFM_ABI_VERSION at load time.
  * 100: rounds 1-3; 101: osfm_ba_summary.flow_fallbacks, osfm_match_stats.surf_*; 102: one observation per camera
  * and point enforced, osfm_scene_set_cameras,
- * osfm_ba_summary.order_arcs / chain_blocks*. */
+ * osfm_ba_summary.order_arcs / chain_blocks*.  New entries and new structs (the view front end) leave it alone:
+ * nothing that a caller built against 102 reads or writes has changed. */
 #define OSFM_ABI_VERSION 102
 OSFM_API int osfm_version(void);
 /* Number of visible HIP devices (0 when there is none). */
@@ -886,8 +887,9 @@ OSFM_API int osfm_time_measurements_read(const char *path, double *seconds);
  * feature_set.cc:42-86), on the device.  The octave and DoG images, the candidate
  * list and the localised keypoints are equal to the reference's bytes; orientations
  * and descriptors are the same algorithm evaluated in double (DESIGN.md has the
- * measured distance).  Image files and the max_image_size halving loop of
- * bundler_features.cc:66-68 stay with the caller; SURF is the next section.
+ * measured distance).  This entry takes the image as the detector sees it; the
+ * max_image_size halving loop of bundler_features.cc:66-68 is the view front end's
+ * (last section).  SURF is the next section.
  * ------------------------------------------------------------------------- */
 #define OSFM_SIFT_MAX_OCTAVES 16
 
@@ -956,7 +958,8 @@ OSFM_API int osfm_sift_debug_keypoints(osfm_sift *ctx, int after_localisation, f
  * the values of expf, atan2, sinf and cosf taken from the host's C library.  The one
  * decision that cannot be pinned is the orientation window test of a sample whose
  * atan2f lies within a few ulps of a window bound (DESIGN.md 3u counts them).
- * Image files and the max_image_size halving loop stay with the caller.
+ * This entry takes the image as the detector sees it; the halving loop is the view
+ * front end's (last section).
  * ------------------------------------------------------------------------- */
 #define OSFM_SURF_OCTAVES 4
 
@@ -1019,6 +1022,98 @@ OSFM_API int osfm_surf_debug_image(osfm_surf *ctx, int octave, int sample, float
 OSFM_API int osfm_surf_debug_keypoints(osfm_surf *ctx, int after_localisation, float *out, int32_t *count);
 OSFM_API int osfm_surf_debug_describe(osfm_surf *ctx, float x, float y, float scale, float orientation, int upright,
     float *out, int32_t *status);
+
+/* ---------------------------------------------------------------------------
+ * View front end: bundler::Features::compute and the image part of calculateTracksUsingMVE
+ * (matching_mve.cpp:144-152, bundler_features.cc:66-68) from a decoded byte image in host
+ * memory to a view of a matcher.  One upload; the halving chain, both detectors, FeatureSet's
+ * colours and normalised positions and the quantised bank of the matcher are made on the
+ * device, and the float descriptors never cross the bus.  Image files, EXIF and .mve scenes
+ * stay with the caller.
+ * ------------------------------------------------------------------------- */
+#define OSFM_FEATURE_SIFT 1
+#define OSFM_FEATURE_SURF 2
+#define OSFM_FEATURE_ALL 3
+
+typedef struct osfm_view_options {
+    int32_t downscale_factor;   /* 1: downscale_image runs downscale_factor - 1 halvings */
+    int32_t max_image_size;     /* 6000000 (AppSettings); <= 0: no limit.  The image is halved while
+                                   width * height > max_image_size, in int arithmetic as in the reference */
+    int32_t feature_types;      /* OSFM_FEATURE_SIFT, OSFM_FEATURE_SURF or OSFM_FEATURE_ALL (the default) */
+} osfm_view_options;
+OSFM_API int osfm_view_options_default(osfm_view_options *opts);
+
+typedef struct osfm_view_summary {
+    int32_t import_width, import_height;      /* after downscale_factor: the reference's imageWidth */
+    int32_t feature_width, feature_height;    /* after the max_image_size loop: what the detectors saw */
+    int32_t num_halvings, num_sift, num_surf, reserved;
+    osfm_sift_summary sift;                   /* zero where the detector did not run */
+    osfm_surf_summary surf;
+    /* device events: the halving chain, the colour and position kernel, and their sum with both detectors' total_ms */
+    double halving_ms, view_ms, total_ms;
+} osfm_view_summary;
+
+typedef struct osfm_view_front osfm_view_front;
+
+/* A front end owns two image buffers for inputs up to max_width x max_height x 3, a SIFT and a SURF context (per
+ * feature_types) and the arrays of one view, all booked in osfm_library_memory.  The contexts are sized for the
+ * largest image the chain can hand them: the input bound after the downscale_factor - 1 halvings, since an image
+ * under max_image_size passes the loop as it is.  Any of the options may be NULL: the defaults. */
+OSFM_API int osfm_view_front_create(int device, int max_width, int max_height, const osfm_view_options *view_opts,
+    const osfm_sift_options *sift_opts, const osfm_surf_options *surf_opts, osfm_view_front **out);
+OSFM_API int osfm_view_front_destroy(osfm_view_front *front);
+
+/* Uploads an 8-bit image (row-major, channels interleaved, 1 or 3 channels), runs the halving chain
+ * (mve::image::rescale_half_size<uint8_t>) and the detectors on its result, and computes colours and normalised
+ * positions from the device image.  The result stays in the front end until the next call.  A call waits on the
+ * device -- not on the host -- for an osfm_match_set_view_from_front that still reads the previous result.
+ * Errors, none of which writes *summary or leaves a result behind:
+ *   OSFM_E_ARG       channels other than 1 or 3; a size on which the reference throws: a halving of an image with a
+ *                    side below 2, or an image the SIFT detector refuses (osfm_sift_extract)
+ *   OSFM_E_RANGE     an image larger than max_width x max_height
+ *   OSFM_E_CAPACITY  as osfm_sift_extract / osfm_surf_extract */
+OSFM_API int osfm_view_front_load(osfm_view_front *front, const uint8_t *pixels, int width, int height, int channels,
+    osfm_view_summary *summary);
+
+/* The last load in FeatureSet's order, SIFT rows first then SURF rows, each by scale descending; every output is
+ * caller-allocated and may be NULL.  With n = num_sift + num_surf:
+ *   positions [n][2] (pixels of the feature image), normalized [n][2], colors [n][3], scale [n], orientation [n],
+ *   sift_descriptors [num_sift][128], surf_descriptors [num_surf][64] */
+OSFM_API int osfm_view_front_download(osfm_view_front *front, float *positions, float *normalized, uint8_t *colors, float *scale,
+    float *orientation, float *sift_descriptors, float *surf_descriptors);
+
+/* Test hook: the image the detectors saw; *width, *height, *channels (may be NULL) are always set, out (may be
+ * NULL) takes width * height * channels bytes. */
+OSFM_API int osfm_view_front_debug_image(osfm_view_front *front, uint8_t *out, int32_t *width, int32_t *height, int32_t *channels);
+
+/* Sets view `view` of the matcher from the front end's last load, on the device: what osfm_view_front_download ->
+ * osfm_match_set_view_float -> osfm_match_set_positions (normalised, SIFT rows then SURF rows) would leave, byte for
+ * byte.  As in osfm_match_set_view the work is queued on the matcher's upload stream, here behind an event of the
+ * front end's stream, and the host waits only for two scalars (the number of special rows and the largest SURF
+ * norm).  A multi-device matcher prepares the view on the first shard on the front end's device and copies the
+ * prepared arrays to the others, device to device.
+ *   OSFM_E_STATE  no load to hand off
+ *   OSFM_E_ARG    the front end's device is none of the matcher's; a view id out of range
+ * Neither touches the view. */
+OSFM_API int osfm_match_set_view_from_front(osfm_matcher *m, int view, osfm_view_front *front);
+
+/* Test hooks.  osfm_match_debug_view_bank: every array of a view that a matching call reads, in padded length.  The
+ * counts are always set; each pointer may be NULL.  Lengths: sift, sift_raw [n_sift_pad][128]; sift_corr,
+ * sift_raw_corr [n_sift_pad]; special [n_special_pad][128], special_corr [n_special_pad], special_map [n_special],
+ * special_slot [n_sift] (the last four only where n_special > 0); surf [n_surf_pad][64], surf_corr [n_surf_pad];
+ * positions [n_positions][2] (n_positions -1: never set).
+ * osfm_match_debug_set_view_device: float rows in HOST memory and optional permutations (row i of the view is row
+ * order[i]; NULL: the identity) are put on the device as they are and go through the device hand-off of
+ * osfm_match_set_view_from_front, positions [n_sift + n_surf][2] included: values that no detector produces. */
+typedef struct osfm_view_bank {
+    int32_t n_sift, n_surf, n_sift_pad, n_surf_pad, n_special, n_special_pad, surf_norm2_max, n_positions;
+    int8_t *sift, *sift_raw, *special, *surf;
+    int32_t *sift_corr, *sift_raw_corr, *special_corr, *special_map, *special_slot, *surf_corr;
+    float *positions;
+} osfm_view_bank;
+OSFM_API int osfm_match_debug_view_bank(osfm_matcher *m, int view, int shard, osfm_view_bank *bank);
+OSFM_API int osfm_match_debug_set_view_device(osfm_matcher *m, int view, const float *sift, int n_sift, const int32_t *sift_order,
+    const float *surf, int n_surf, const int32_t *surf_order, const float *positions);
 
 #ifdef __cplusplus
 }

@@ -180,6 +180,30 @@ class SurfSummary(C.Structure):
                                           "descriptor_ms", "total_ms")]
 
 
+FEATURE_SIFT, FEATURE_SURF, FEATURE_ALL = 1, 2, 3
+
+
+class ViewOptions(C.Structure):
+    """osfm_view_options"""
+    _fields_ = [("downscale_factor", C.c_int32), ("max_image_size", C.c_int32), ("feature_types", C.c_int32)]
+
+
+class ViewSummary(C.Structure):
+    """osfm_view_summary"""
+    _fields_ = [(n, C.c_int32) for n in ("import_width", "import_height", "feature_width", "feature_height", "num_halvings",
+                                         "num_sift", "num_surf", "reserved")] + \
+               [("sift", SiftSummary), ("surf", SurfSummary)] + \
+               [(n, C.c_double) for n in ("halving_ms", "view_ms", "total_ms")]
+
+
+class ViewBank(C.Structure):
+    """osfm_view_bank (test hook osfm_match_debug_view_bank)."""
+    COUNTS = ("n_sift", "n_surf", "n_sift_pad", "n_surf_pad", "n_special", "n_special_pad", "surf_norm2_max", "n_positions")
+    ARRAYS = ("sift", "sift_raw", "special", "surf", "sift_corr", "sift_raw_corr", "special_corr", "special_map", "special_slot",
+              "surf_corr", "positions")
+    _fields_ = [(n, C.c_int32) for n in COUNTS] + [(n, C.c_void_p) for n in ARRAYS]
+
+
 class BaLinCapture(C.Structure):
     """osfm_ba_lin_capture (test hook osfm_ba_debug_linearization)."""
     ARRAYS = ("scale_c", "diag_c", "S", "rhs", "scale_p", "diag_p", "vinv", "ge", "y_c", "cand_cams", "cand_points")
@@ -221,6 +245,9 @@ EXPORTS = [
     "osfm_sift_debug_image", "osfm_sift_debug_keypoints",
     "osfm_surf_options_default", "osfm_surf_create", "osfm_surf_destroy", "osfm_surf_extract", "osfm_surf_download",
     "osfm_surf_debug_image", "osfm_surf_debug_keypoints", "osfm_surf_debug_describe",
+    "osfm_view_options_default", "osfm_view_front_create", "osfm_view_front_destroy", "osfm_view_front_load",
+    "osfm_view_front_download", "osfm_view_front_debug_image", "osfm_match_set_view_from_front",
+    "osfm_match_debug_view_bank", "osfm_match_debug_set_view_device",
 ]
 
 # osfm_track_feature as a numpy record (32 bytes, no padding)
@@ -252,6 +279,16 @@ lib.osfm_surf_debug_image.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, 
 lib.osfm_surf_debug_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
 lib.osfm_surf_debug_describe.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_int32)]
+lib.osfm_view_front_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(ViewOptions), C.POINTER(SiftOptions),
+                                       C.POINTER(SurfOptions), C.POINTER(C.c_void_p)]
+lib.osfm_view_front_destroy.argtypes = [C.c_void_p]
+lib.osfm_view_front_load.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewSummary)]
+lib.osfm_view_front_download.argtypes = [C.c_void_p] + [C.c_void_p] * 7
+lib.osfm_view_front_debug_image.argtypes = [C.c_void_p, C.c_void_p] + [C.POINTER(C.c_int32)] * 3
+lib.osfm_match_set_view_from_front.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+lib.osfm_match_debug_view_bank.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(ViewBank)]
+lib.osfm_match_debug_set_view_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_void_p]
 lib.osfm_ba_debug_cholesky_solve.restype = C.c_int
 lib.osfm_ba_debug_cholesky_solve.argtypes = [C.c_int, C.c_int, _f64p, _f64p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, _f64p, _i32p, _i32p]
@@ -345,6 +382,12 @@ def default_sift_options() -> SiftOptions:
 def default_surf_options() -> SurfOptions:
     o = SurfOptions()
     check(lib.osfm_surf_options_default(C.byref(o)))
+    return o
+
+
+def default_view_options() -> ViewOptions:
+    o = ViewOptions()
+    check(lib.osfm_view_options_default(C.byref(o)))
     return o
 
 

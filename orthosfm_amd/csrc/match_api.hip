@@ -20,6 +20,8 @@
 #include <random>
 #include "osfm_common.h"
 #include "ransac_kernels.h"
+#include "view_front.h"
+#include "view_kernels.h"
 
 namespace osfm {
 
@@ -750,6 +752,128 @@ int upload_view(osfm_matcher *m, int view, const uint16_t *sift, int n_sift, con
     return OSFM_OK;
 }
 
+// upload_view's result from float rows that are on this matcher's device already (the view front end's hand-off):
+// row i of the view is row sift_map[i] of d_sift (NULL: row i), likewise SURF; d_positions holds ns + nu rows.
+// Queued on the upload stream like upload_view; the host waits once, for the number of special rows (which sizes
+// their gathered set) and the largest SURF norm.  The caller has made the stream wait for the source arrays.
+int handoff_view(osfm_matcher *m, int view, const float *d_sift, const int32_t *sift_map, int n_sift, const float *d_surf,
+    const int32_t *surf_map, int n_surf, const float *d_positions)
+{
+    ViewData &v = m->views[view];
+    hipStream_t s = m->up_stream;
+    v.set = false;
+    v.ns = n_sift; v.nu = n_surf;
+    v.ns_pad = round_up(std::max(n_sift, 1), kRowsPerBlock);
+    v.nu_pad = round_up(std::max(n_surf, 1), kRowsPerBlock);
+    OSFM_RETURN_IF(v.sift.reserve((size_t)v.ns_pad * 128));
+    OSFM_RETURN_IF(v.sift_corr.reserve((size_t)v.ns_pad * 4));
+    OSFM_RETURN_IF(v.sift_raw.reserve((size_t)v.ns_pad * 128));
+    OSFM_RETURN_IF(v.sift_raw_corr.reserve((size_t)v.ns_pad * 4));
+    OSFM_RETURN_IF(v.surf.reserve((size_t)v.nu_pad * 64));
+    OSFM_RETURN_IF(v.surf_corr.reserve((size_t)v.nu_pad * 4));
+    // the scan writes both before the number of special rows is known: sized for every row
+    OSFM_RETURN_IF(v.special_slot.reserve((size_t)std::max(n_sift, 1) * 4));
+    OSFM_RETURN_IF(v.special_map.reserve((size_t)std::max(n_sift, 1) * 4));
+    OSFM_RETURN_IF(v.positions.reserve((size_t)std::max(n_sift + n_surf, 1) * 8));
+    OSFM_RETURN_IF(m->flags.reserve(16));
+    int32_t *scalars = m->flags.as<int32_t>();     // [0]: special rows, [1]: largest SURF norm
+    OSFM_HIP_CHECK(hipMemsetAsync(scalars, 0, 8, s));
+    view::launch_handoff_sift(s, d_sift, sift_map, n_sift, v.ns_pad, v.sift.as<int8_t>(), v.sift_corr.as<int32_t>(),
+        v.sift_raw.as<int8_t>(), v.sift_raw_corr.as<int32_t>(), v.special_slot.as<int32_t>());
+    view::launch_special_scan(s, v.special_slot.as<int32_t>(), n_sift, v.special_map.as<int32_t>(), scalars + 0);
+    view::launch_handoff_surf(s, d_surf, surf_map, n_surf, v.nu_pad, v.surf.as<int8_t>(), v.surf_corr.as<int32_t>(), scalars + 1);
+    if (n_sift + n_surf)
+        OSFM_HIP_CHECK(hipMemcpyAsync(v.positions.ptr, d_positions, (size_t)(n_sift + n_surf) * 8, hipMemcpyDeviceToDevice, s));
+    OSFM_HIP_CHECK(hipGetLastError());
+    int32_t h_scalars[2] = {0, 0};
+    OSFM_HIP_CHECK(hipMemcpyAsync(h_scalars, scalars, 8, hipMemcpyDeviceToHost, s));
+    OSFM_HIP_CHECK(hipStreamSynchronize(s));
+    v.n_special = h_scalars[0];
+    if (v.n_special > 0) {
+        const int sp_pad = round_up(v.n_special, kRowsPerBlock);
+        OSFM_RETURN_IF(v.special.reserve((size_t)sp_pad * 128));
+        OSFM_RETURN_IF(v.special_corr.reserve((size_t)sp_pad * 4));
+        launch_gather_rows(v.sift.as<int8_t>(), v.sift_corr.as<int32_t>(), v.special_map.as<int32_t>(),
+            v.n_special, sp_pad, 128, -(1 << 20) - (1 << 22), (int8_t)-128, v.special.as<int8_t>(),
+            v.special_corr.as<int32_t>(), s);
+        OSFM_HIP_CHECK(hipGetLastError());
+    }
+    if (!v.ready) OSFM_HIP_CHECK(event_create(&v.ready, false));
+    OSFM_HIP_CHECK(hipEventRecord(v.ready, s));
+    v.surf_norm2_max = h_scalars[1];
+    v.n_positions = n_sift + n_surf;
+    v.set = true;
+    m->cas_dirty = true;
+    return OSFM_OK;
+}
+
+// View `view` of `src` (prepared, possibly on another device) into the same view of `dst`, array for array.
+int copy_view(osfm_matcher *dst, osfm_matcher *src, int view)
+{
+    std::lock_guard<std::mutex> lock(dst->up_mu);
+    OSFM_HIP_CHECK(hipSetDevice(dst->device));
+    const ViewData &a = src->views[view];
+    ViewData &v = dst->views[view];
+    hipStream_t s = dst->up_stream;
+    v.set = false;
+    v.ns = a.ns; v.nu = a.nu; v.ns_pad = a.ns_pad; v.nu_pad = a.nu_pad;
+    v.n_special = a.n_special; v.surf_norm2_max = a.surf_norm2_max; v.n_positions = a.n_positions;
+    OSFM_HIP_CHECK(hipStreamWaitEvent(s, a.ready, 0));
+    const int sp_pad = a.n_special > 0 ? round_up(a.n_special, kRowsPerBlock) : 0;
+    struct { DeviceBuffer *to; const DeviceBuffer *from; size_t bytes; } arrays[] = {
+        {&v.sift, &a.sift, (size_t)a.ns_pad * 128}, {&v.sift_corr, &a.sift_corr, (size_t)a.ns_pad * 4},
+        {&v.sift_raw, &a.sift_raw, (size_t)a.ns_pad * 128}, {&v.sift_raw_corr, &a.sift_raw_corr, (size_t)a.ns_pad * 4},
+        {&v.surf, &a.surf, (size_t)a.nu_pad * 64}, {&v.surf_corr, &a.surf_corr, (size_t)a.nu_pad * 4},
+        {&v.special, &a.special, (size_t)sp_pad * 128}, {&v.special_corr, &a.special_corr, (size_t)sp_pad * 4},
+        {&v.special_map, &a.special_map, sp_pad ? (size_t)a.n_special * 4 : 0},
+        {&v.special_slot, &a.special_slot, sp_pad ? (size_t)a.ns * 4 : 0},
+        {&v.positions, &a.positions, (size_t)std::max(a.n_positions, 0) * 8},
+    };
+    for (auto &r : arrays) {
+        if (!r.bytes) continue;
+        OSFM_RETURN_IF(r.to->reserve(r.bytes));
+        OSFM_HIP_CHECK(hipMemcpyAsync(r.to->ptr, r.from->ptr, r.bytes, hipMemcpyDefault, s));
+    }
+    if (!v.ready) OSFM_HIP_CHECK(event_create(&v.ready, false));
+    OSFM_HIP_CHECK(hipEventRecord(v.ready, s));
+    v.set = true;
+    dst->cas_dirty = true;
+    return OSFM_OK;
+}
+
+// The device hand-off on a matcher of one or several shards: prepared once, on the first shard on `device`, and
+// copied to the others.  begin / end bracket the reads of the source arrays on that shard's upload stream.
+template <class Begin, class End>
+int handoff_all(osfm_matcher *m, int view, int device, const float *d_sift, const int32_t *sift_map, int n_sift,
+    const float *d_surf, const int32_t *surf_map, int n_surf, const float *d_positions, Begin &&begin, End &&end)
+{
+    osfm_matcher *first = m;
+    if (!m->shards.empty()) {
+        first = nullptr;
+        for (auto *sh : m->shards)
+            if (sh->device == device) { first = sh; break; }
+    }
+    if (!first || first->device != device) {
+        set_error("set_view_from_front: the descriptors are on device %d, which is none of the matcher's", device);
+        return OSFM_E_ARG;
+    }
+    if (view < 0 || view >= (int)first->views.size()) {
+        set_error("set_view_from_front: view id %d out of range", view);
+        return OSFM_E_ARG;
+    }
+    {
+        std::lock_guard<std::mutex> lock(first->up_mu);
+        OSFM_HIP_CHECK(hipSetDevice(first->device));
+        OSFM_RETURN_IF(begin(first->up_stream));
+        const int rc = handoff_view(first, view, d_sift, sift_map, n_sift, d_surf, surf_map, n_surf, d_positions);
+        OSFM_RETURN_IF(end(first->up_stream));
+        OSFM_RETURN_IF(rc);
+    }
+    for (auto *sh : m->shards)
+        if (sh != first) OSFM_RETURN_IF(copy_view(sh, first, view));
+    return OSFM_OK;
+}
+
 // CascadeHashing::init (cascade_hashing.cc:33-70) for the views set so far.
 // The projection matrices are drawn on the host with the same standard-library
 // facilities the reference uses (std::mt19937(0) + std::normal_distribution<>,
@@ -1346,6 +1470,76 @@ int osfm_match_set_positions(osfm_matcher *m, int view, const float *xy, int n)
     OSFM_RETURN_IF(v.positions.reserve((size_t)std::max(n, 1) * 8));
     if (n) OSFM_HIP_CHECK(hipMemcpy(v.positions.ptr, xy, (size_t)n * 8, hipMemcpyHostToDevice));
     v.n_positions = n;
+    return OSFM_OK;
+}
+
+int osfm_match_set_view_from_front(osfm_matcher *m, int view, osfm_view_front *front)
+{
+    if (!m || !front) { set_error("set_view_from_front: null argument"); return OSFM_E_ARG; }
+    FrontResult r;
+    OSFM_RETURN_IF(view_front_result(front, &r));
+    return handoff_all(m, view, r.device, r.sift_desc, r.sift_map, r.n_sift, r.surf_desc, r.surf_map, r.n_surf, r.normalized,
+        [&](hipStream_t s) { return view_front_begin_read(front, s); }, [&](hipStream_t s) { return view_front_end_read(front, s); });
+}
+
+int osfm_match_debug_set_view_device(osfm_matcher *m, int view, const float *sift, int n_sift, const int32_t *sift_order,
+    const float *surf, int n_surf, const int32_t *surf_order, const float *positions)
+{
+    if (!m || n_sift < 0 || n_surf < 0 || (n_sift > 0 && !sift) || (n_surf > 0 && !surf) || (n_sift + n_surf > 0 && !positions)) {
+        set_error("debug_set_view_device: bad arguments");
+        return OSFM_E_ARG;
+    }
+    for (int i = 0; i < n_sift; ++i)
+        if (sift_order && (sift_order[i] < 0 || sift_order[i] >= n_sift)) { set_error("debug_set_view_device: sift_order[%d] out of range", i); return OSFM_E_ARG; }
+    for (int i = 0; i < n_surf; ++i)
+        if (surf_order && (surf_order[i] < 0 || surf_order[i] >= n_surf)) { set_error("debug_set_view_device: surf_order[%d] out of range", i); return OSFM_E_ARG; }
+    const int device = m->shards.empty() ? m->device : m->shards[0]->device;
+    OSFM_HIP_CHECK(hipSetDevice(device));
+    DeviceBuffer d_sift, d_surf, d_so, d_uo, d_pos;
+    auto put = [](DeviceBuffer &b, const void *src, size_t bytes) -> int {
+        if (!src || !bytes) return OSFM_OK;
+        OSFM_RETURN_IF(b.reserve(bytes));
+        OSFM_HIP_CHECK(hipMemcpy(b.ptr, src, bytes, hipMemcpyHostToDevice));
+        return OSFM_OK;
+    };
+    OSFM_RETURN_IF(put(d_sift, sift, (size_t)n_sift * 128 * 4));
+    OSFM_RETURN_IF(put(d_surf, surf, (size_t)n_surf * 64 * 4));
+    OSFM_RETURN_IF(put(d_so, sift_order, (size_t)n_sift * 4));
+    OSFM_RETURN_IF(put(d_uo, surf_order, (size_t)n_surf * 4));
+    OSFM_RETURN_IF(put(d_pos, positions, (size_t)(n_sift + n_surf) * 8));
+    hipStream_t used = nullptr;
+    const int rc = handoff_all(m, view, device, d_sift.as<float>(), d_so.as<int32_t>(), n_sift, d_surf.as<float>(), d_uo.as<int32_t>(),
+        n_surf, d_pos.as<float>(), [&](hipStream_t s) -> int { used = s; return OSFM_OK; }, [](hipStream_t) -> int { return OSFM_OK; });
+    if (used) (void)hipStreamSynchronize(used);      // the source arrays go with this call
+    return rc;
+}
+
+int osfm_match_debug_view_bank(osfm_matcher *m, int view, int shard, osfm_view_bank *b)
+{
+    if (!m || !b) { set_error("debug_view_bank: null argument"); return OSFM_E_ARG; }
+    if (!m->shards.empty()) {
+        if (shard < 0 || shard >= (int)m->shards.size()) { set_error("debug_view_bank: shard %d of %zu", shard, m->shards.size()); return OSFM_E_ARG; }
+        return osfm_match_debug_view_bank(m->shards[(size_t)shard], view, 0, b);
+    }
+    std::lock_guard<std::mutex> lock(m->up_mu);
+    OSFM_HIP_CHECK(hipSetDevice(m->device));
+    OSFM_RETURN_IF(check_view(m, view, "debug_view_bank"));
+    const ViewData &v = m->views[view];
+    OSFM_HIP_CHECK(hipStreamSynchronize(m->up_stream));
+    const int sp_pad = v.n_special > 0 ? round_up(v.n_special, kRowsPerBlock) : 0;
+    b->n_sift = v.ns; b->n_surf = v.nu; b->n_sift_pad = v.ns_pad; b->n_surf_pad = v.nu_pad;
+    b->n_special = v.n_special; b->n_special_pad = sp_pad; b->surf_norm2_max = v.surf_norm2_max; b->n_positions = v.n_positions;
+    struct { void *to; const DeviceBuffer *from; size_t bytes; } arrays[] = {
+        {b->sift, &v.sift, (size_t)v.ns_pad * 128}, {b->sift_corr, &v.sift_corr, (size_t)v.ns_pad * 4},
+        {b->sift_raw, &v.sift_raw, (size_t)v.ns_pad * 128}, {b->sift_raw_corr, &v.sift_raw_corr, (size_t)v.ns_pad * 4},
+        {b->surf, &v.surf, (size_t)v.nu_pad * 64}, {b->surf_corr, &v.surf_corr, (size_t)v.nu_pad * 4},
+        {b->special, &v.special, (size_t)sp_pad * 128}, {b->special_corr, &v.special_corr, (size_t)sp_pad * 4},
+        {b->special_map, &v.special_map, sp_pad ? (size_t)v.n_special * 4 : 0},
+        {b->special_slot, &v.special_slot, sp_pad ? (size_t)v.ns * 4 : 0},
+        {b->positions, &v.positions, (size_t)std::max(v.n_positions, 0) * 8},
+    };
+    for (auto &r : arrays)
+        if (r.to && r.bytes) OSFM_HIP_CHECK(hipMemcpy(r.to, r.from->ptr, r.bytes, hipMemcpyDeviceToHost));
     return OSFM_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <memory>
 #include <numeric>
 
+#include "feature_device.h"
 #include "feature_view.h"
 #include "osfm_common.h"
 #include "sift_kernels.h"
@@ -116,7 +117,10 @@ int copy_image(osfm_sift *c, const float *src, int w, int h, float *out)
     return OSFM_OK;
 }
 
-int extract(osfm_sift *c, const uint8_t *pixels, int width, int height, int channels, osfm_sift_summary *sum_out)
+// pixels: the image in host memory, uploaded here; or NULL with d_pixels, the image on the device, read once
+// image_ready has happened (the colours and normalised positions then stay with the caller).
+int extract(osfm_sift *c, const uint8_t *pixels, const uint8_t *d_pixels, hipEvent_t image_ready, int width, int height,
+    int channels, osfm_sift_summary *sum_out)
 {
     const osfm_sift_options &o = c->opts;
     const int S = o.num_samples_per_octave;
@@ -164,8 +168,11 @@ int extract(osfm_sift *c, const uint8_t *pixels, int width, int height, int chan
     // ---- scale space
     OSFM_HIP_CHECK(hipEventRecord(c->ev[0], s));
     const size_t bytes = (size_t)width * height * channels;
-    OSFM_HIP_CHECK(hipMemcpyAsync(c->pixels.ptr, pixels, bytes, hipMemcpyHostToDevice, s));
-    launch_to_float(s, c->pixels.as<uint8_t>(), width, height, channels, orig);
+    if (pixels) {
+        OSFM_HIP_CHECK(hipMemcpyAsync(c->pixels.ptr, pixels, bytes, hipMemcpyHostToDevice, s));
+        d_pixels = c->pixels.as<uint8_t>();
+    } else if (image_ready) OSFM_HIP_CHECK(hipStreamWaitEvent(s, image_ready, 0));
+    launch_to_float(s, d_pixels, width, height, channels, orig);
     const float hs = 0.866025403784439f;       // rescale_half_size_gaussian's default sigma
     const float hw1 = std::exp(-0.5f / (2.0f * (hs * hs))), hw2 = std::exp(-2.5f / (2.0f * (hs * hs))),
                 hw3 = std::exp(-4.5f / (2.0f * (hs * hs)));
@@ -300,7 +307,7 @@ int extract(osfm_sift *c, const uint8_t *pixels, int width, int height, int chan
         c->positions[2 * (size_t)j] = x; c->positions[2 * (size_t)j + 1] = y;
         c->scale[(size_t)j] = abs_scale[(size_t)jobs[(size_t)j].keypoint];
         c->orientation[(size_t)j] = jobs[(size_t)j].orientation;
-        feature_view_row(pixels, width, height, channels, x, y, &c->colors[3 * (size_t)j], &c->normalized[2 * (size_t)j]);
+        if (pixels) feature_view_row(pixels, width, height, channels, x, y, &c->colors[3 * (size_t)j], &c->normalized[2 * (size_t)j]);
     }
     feature_view_order(c->scale, &c->order);
     float ms[5] = {};
@@ -316,7 +323,48 @@ int extract(osfm_sift *c, const uint8_t *pixels, int width, int height, int chan
     return OSFM_OK;
 }
 
+// What osfm_sift_extract checks before it runs
+int check_image(osfm_sift *c, int width, int height, int channels)
+{
+    if (channels != 1 && channels != 3) {
+        set_error("osfm_sift_extract: %d channels: a grey (1) or colour (3) image is expected", channels);
+        return OSFM_E_ARG;
+    }
+    if (width < 1 || height < 1) { set_error("osfm_sift_extract: image size %d x %d", width, height); return OSFM_E_ARG; }
+    if (width > c->max_w || height > c->max_h) {
+        set_error("osfm_sift_extract: a %d x %d image exceeds the context's %d x %d", width, height, c->max_w, c->max_h);
+        return OSFM_E_RANGE;
+    }
+    return OSFM_OK;
+}
+
 }  // namespace
+
+namespace osfm {
+
+int sift_extract_device(osfm_sift *c, const uint8_t *d_pixels, hipEvent_t image_ready, int width, int height, int channels,
+    osfm_sift_summary *summary)
+{
+    if (!c || !d_pixels) { set_error("osfm_sift_extract: null argument"); return OSFM_E_ARG; }
+    c->have = false;
+    OSFM_RETURN_IF(check_image(c, width, height, channels));
+    OSFM_HIP_CHECK(hipSetDevice(c->device));
+    const int rc = extract(c, nullptr, d_pixels, image_ready, width, height, channels, summary);
+    if (rc != OSFM_OK) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int sift_device_features(osfm_sift *c, DeviceFeatures *out)
+{
+    if (!c || !out) { set_error("osfm_sift: null argument"); return OSFM_E_ARG; }
+    if (!c->have) { set_error("osfm_sift: no extraction"); return OSFM_E_STATE; }
+    out->desc = c->desc.as<float>(); out->n = c->n_desc;
+    out->positions = &c->positions; out->scale = &c->scale; out->orientation = &c->orientation;
+    out->order = &c->order; out->rows = nullptr;
+    return OSFM_OK;
+}
+
+}  // namespace osfm
 
 extern "C" {
 
@@ -418,17 +466,9 @@ int osfm_sift_extract(osfm_sift *c, const uint8_t *pixels, int width, int height
 {
     if (!c || !pixels) { set_error("osfm_sift_extract: null argument"); return OSFM_E_ARG; }
     c->have = false;          // whatever comes of this call, the previous result is gone
-    if (channels != 1 && channels != 3) {
-        set_error("osfm_sift_extract: %d channels: a grey (1) or colour (3) image is expected", channels);
-        return OSFM_E_ARG;
-    }
-    if (width < 1 || height < 1) { set_error("osfm_sift_extract: image size %d x %d", width, height); return OSFM_E_ARG; }
-    if (width > c->max_w || height > c->max_h) {
-        set_error("osfm_sift_extract: a %d x %d image exceeds the context's %d x %d", width, height, c->max_w, c->max_h);
-        return OSFM_E_RANGE;
-    }
+    OSFM_RETURN_IF(check_image(c, width, height, channels));
     OSFM_HIP_CHECK(hipSetDevice(c->device));
-    const int rc = extract(c, pixels, width, height, channels, summary);
+    const int rc = extract(c, pixels, nullptr, nullptr, width, height, channels, summary);
     if (rc != OSFM_OK) (void)hipStreamSynchronize(c->stream);   // nothing of a failed call may still run
     return rc;
 }

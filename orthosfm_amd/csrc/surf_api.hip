@@ -7,6 +7,7 @@
 #include <cstring>
 #include <memory>
 
+#include "feature_device.h"
 #include "feature_view.h"
 #include "osfm_common.h"
 #include "surf_kernels.h"
@@ -81,7 +82,10 @@ int describe(osfm_surf *c, const std::vector<DescJob> &jobs, std::vector<int32_t
     return OSFM_OK;
 }
 
-int extract(osfm_surf *c, const uint8_t *pixels, int width, int height, int channels, osfm_surf_summary *sum_out)
+// pixels: the image in host memory, uploaded here; or NULL with d_pixels, the image on the device, read once
+// image_ready has happened (the colours and normalised positions then stay with the caller).
+int extract(osfm_surf *c, const uint8_t *pixels, const uint8_t *d_pixels, hipEvent_t image_ready, int width, int height,
+    int channels, osfm_surf_summary *sum_out)
 {
     const osfm_surf_options &o = c->opts;
     hipStream_t s = c->stream;
@@ -96,8 +100,11 @@ int extract(osfm_surf *c, const uint8_t *pixels, int width, int height, int chan
 
     // ---- summed-area table
     OSFM_HIP_CHECK(hipEventRecord(c->ev[0], s));
-    OSFM_HIP_CHECK(hipMemcpyAsync(c->pixels.ptr, pixels, (size_t)width * height * channels, hipMemcpyHostToDevice, s));
-    launch_sat(s, c->pixels.as<uint8_t>(), width, height, channels, sat);
+    if (pixels) {
+        OSFM_HIP_CHECK(hipMemcpyAsync(c->pixels.ptr, pixels, (size_t)width * height * channels, hipMemcpyHostToDevice, s));
+        d_pixels = c->pixels.as<uint8_t>();
+    } else if (image_ready) OSFM_HIP_CHECK(hipStreamWaitEvent(s, image_ready, 0));
+    launch_sat(s, d_pixels, width, height, channels, sat);
 
     // ---- response maps
     OSFM_HIP_CHECK(hipEventRecord(c->ev[1], s));
@@ -217,7 +224,7 @@ int extract(osfm_surf *c, const uint8_t *pixels, int width, int height, int chan
         c->positions[2 * (size_t)r] = k.x; c->positions[2 * (size_t)r + 1] = k.y;
         c->scale[(size_t)r] = kp_scale[(size_t)job_kp[j]];
         c->orientation[(size_t)r] = job_ori[j];
-        feature_view_row(pixels, width, height, channels, k.x, k.y, &c->colors[3 * (size_t)r], &c->normalized[2 * (size_t)r]);
+        if (pixels) feature_view_row(pixels, width, height, channels, k.x, k.y, &c->colors[3 * (size_t)r], &c->normalized[2 * (size_t)r]);
     }
     feature_view_order(c->scale, &c->order);
     float ms[6] = {};
@@ -233,7 +240,48 @@ int extract(osfm_surf *c, const uint8_t *pixels, int width, int height, int chan
     return OSFM_OK;
 }
 
+// What osfm_surf_extract checks before it runs
+int check_image(osfm_surf *c, int width, int height, int channels)
+{
+    if (channels != 1 && channels != 3) {
+        set_error("osfm_surf_extract: %d channels: a grey (1) or colour (3) image is expected", channels);
+        return OSFM_E_ARG;
+    }
+    if (width < 1 || height < 1) { set_error("osfm_surf_extract: image size %d x %d", width, height); return OSFM_E_ARG; }
+    if (width > c->max_w || height > c->max_h) {
+        set_error("osfm_surf_extract: a %d x %d image exceeds the context's %d x %d", width, height, c->max_w, c->max_h);
+        return OSFM_E_RANGE;
+    }
+    return OSFM_OK;
+}
+
 }  // namespace
+
+namespace osfm {
+
+int surf_extract_device(osfm_surf *c, const uint8_t *d_pixels, hipEvent_t image_ready, int width, int height, int channels,
+    osfm_surf_summary *summary)
+{
+    if (!c || !d_pixels) { set_error("osfm_surf_extract: null argument"); return OSFM_E_ARG; }
+    c->have = false;
+    OSFM_RETURN_IF(check_image(c, width, height, channels));
+    OSFM_HIP_CHECK(hipSetDevice(c->device));
+    const int rc = extract(c, nullptr, d_pixels, image_ready, width, height, channels, summary);
+    if (rc != OSFM_OK) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int surf_device_features(osfm_surf *c, DeviceFeatures *out)
+{
+    if (!c || !out) { set_error("osfm_surf: null argument"); return OSFM_E_ARG; }
+    if (!c->have) { set_error("osfm_surf: no extraction"); return OSFM_E_STATE; }
+    out->desc = c->desc.as<float>(); out->n = c->n_desc;
+    out->positions = &c->positions; out->scale = &c->scale; out->orientation = &c->orientation;
+    out->order = &c->order; out->rows = &c->rows;
+    return OSFM_OK;
+}
+
+}  // namespace osfm
 
 extern "C" {
 
@@ -323,17 +371,9 @@ int osfm_surf_extract(osfm_surf *c, const uint8_t *pixels, int width, int height
 {
     if (!c || !pixels) { set_error("osfm_surf_extract: null argument"); return OSFM_E_ARG; }
     c->have = false;          // whatever comes of this call, the previous result is gone
-    if (channels != 1 && channels != 3) {
-        set_error("osfm_surf_extract: %d channels: a grey (1) or colour (3) image is expected", channels);
-        return OSFM_E_ARG;
-    }
-    if (width < 1 || height < 1) { set_error("osfm_surf_extract: image size %d x %d", width, height); return OSFM_E_ARG; }
-    if (width > c->max_w || height > c->max_h) {
-        set_error("osfm_surf_extract: a %d x %d image exceeds the context's %d x %d", width, height, c->max_w, c->max_h);
-        return OSFM_E_RANGE;
-    }
+    OSFM_RETURN_IF(check_image(c, width, height, channels));
     OSFM_HIP_CHECK(hipSetDevice(c->device));
-    const int rc = extract(c, pixels, width, height, channels, summary);
+    const int rc = extract(c, pixels, nullptr, nullptr, width, height, channels, summary);
     if (rc != OSFM_OK) (void)hipStreamSynchronize(c->stream);   // nothing of a failed call may still run
     return rc;
 }

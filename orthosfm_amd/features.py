@@ -7,8 +7,14 @@ extraction").
 
     f = SiftExtractor(0, 2048, 2048).extract(image)      # one detector alone; SurfExtractor likewise
 
+    front = ViewFrontEnd(device=0, max_width=4096, max_height=4096)     # include/osfm_hip.h, "View front end"
+    front.load(image)                     # one upload: halving chain, both detectors, colours and positions
+    matcher.set_view_from_front(0, front) # the bank is made on the device; front.download() for the host's copy
+
 A FeatureSet is the reference's with FEATURE_ALL: SIFT rows, then SURF rows, each sorted by scale, descending.
-Reading image files and the halving of images beyond a maximum size stay with the caller.
+The extractors take the image as the detectors see it.  ViewFrontEnd is bundler::Features::compute from a decoded
+image: it halves the image downscale_factor - 1 times and then while it holds more than max_image_size pixels, on
+the device.  Reading image files stays with the caller.
 """
 from __future__ import annotations
 
@@ -232,3 +238,84 @@ class FeatureSetExtractor:
         a, b = self.sift.extract(image), self.surf.extract(image)
         return FeatureSet(a, b, np.concatenate([a.positions, b.positions]), np.concatenate([a.normalized, b.normalized]),
                           np.concatenate([a.colors, b.colors]))
+
+
+@dataclass
+class ViewFeatures(FeatureSet):
+    """What ViewFrontEnd.download returns: the FeatureSet of the image the detectors saw, and the sizes the
+    reference's pixel conversion needs."""
+    import_width: int = 0       # after downscale_factor: calculateTracksUsingMVE's imageWidth
+    import_height: int = 0
+    feature_width: int = 0      # after the max_image_size loop: positions are in pixels of this image
+    feature_height: int = 0
+
+
+class ViewFrontEnd:
+    """One context (osfm_view_front) for images up to max_width x max_height: image in host memory -> halving
+    chain -> SIFT and SURF from one upload -> colours and normalised positions, all on the device.  `sift` and
+    `surf` are dictionaries of the detectors' options."""
+
+    def __init__(self, device: int = 0, max_width: int = 2048, max_height: int = 2048, downscale_factor: int = 1,
+                 max_image_size: int = 6_000_000, feature_types: int = capi.FEATURE_ALL, sift=None, surf=None):
+        vo = capi.ViewOptions(int(downscale_factor), int(max_image_size), int(feature_types))
+        so, uo = capi.default_sift_options(), capi.default_surf_options()
+        for o, given, who in ((so, sift, "sift"), (uo, surf, "surf")):
+            for k, v in (given or {}).items():
+                if not hasattr(o, k):
+                    raise TypeError(f"ViewFrontEnd: unknown {who} option {k!r}")
+                setattr(o, k, v)
+        self.options, self.summary = vo, None
+        self._h = C.c_void_p()
+        capi.check(capi.lib.osfm_view_front_create(device, int(max_width), int(max_height), C.byref(vo), C.byref(so), C.byref(uo),
+                                                   C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            capi.check(capi.lib.osfm_view_front_destroy(self._h))
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def load(self, image) -> capi.ViewSummary:
+        """osfm_view_front_load: the summary (sizes, counts, stage times); the result stays on the device for
+        HipExhaustiveMatching.set_view_from_front and download()."""
+        image, channels = _image_arg("ViewFrontEnd", image)
+        self.summary = None
+        s = capi.ViewSummary()
+        capi.check(capi.lib.osfm_view_front_load(self._h, image.ctypes.data, image.shape[1], image.shape[0], channels, C.byref(s)))
+        self.summary = s
+        return s
+
+    def download(self) -> ViewFeatures:
+        """osfm_view_front_download of the last load()."""
+        if self.summary is None:
+            raise capi.OsfmError(capi.E_STATE, "ViewFrontEnd.download: no load to download")
+        ns, nu = self.summary.num_sift, self.summary.num_surf
+        n = ns + nu
+        pos, nrm, col = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32), np.zeros((n, 3), np.uint8)
+        scale, ori = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        ds, du = np.zeros((ns, 128), np.float32), np.zeros((nu, 64), np.float32)
+        capi.check(capi.lib.osfm_view_front_download(self._h, pos.ctypes.data, nrm.ctypes.data, col.ctypes.data, scale.ctypes.data,
+                                                     ori.ctypes.data, ds.ctypes.data, du.ctypes.data))
+        part = lambda d, a, b: Features(d, pos[a:b], nrm[a:b], scale[a:b], ori[a:b], col[a:b])
+        s = self.summary
+        return ViewFeatures(part(ds, 0, ns), part(du, ns, n), pos, nrm, col, s.import_width, s.import_height, s.feature_width,
+                            s.feature_height)
+
+    def debug_image(self) -> np.ndarray:
+        """Test hook: the image the detectors saw, [h, w] or [h, w, 3]."""
+        w, h, c = C.c_int32(), C.c_int32(), C.c_int32()
+        capi.check(capi.lib.osfm_view_front_debug_image(self._h, None, C.byref(w), C.byref(h), C.byref(c)))
+        out = np.zeros((h.value, w.value) if c.value == 1 else (h.value, w.value, c.value), np.uint8)
+        capi.check(capi.lib.osfm_view_front_debug_image(self._h, out.ctypes.data, None, None, None))
+        return out

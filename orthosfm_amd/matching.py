@@ -100,6 +100,42 @@ class HipExhaustiveMatching:
             self.set_view_float(view, features.descriptors, np.zeros((0, 64), np.float32))
         self.set_positions(view, features.normalized)
 
+    def set_view_from_front(self, view, front):
+        """A view from the last load of a features.ViewFrontEnd, on the device (osfm_match_set_view_from_front): the
+        bank and the positions that set_view_features(view, front.download()) would leave, without the descriptors'
+        way through the host."""
+        capi.check(capi.lib.osfm_match_set_view_from_front(self._h, int(view), front._h))
+
+    # --- test hooks ---------------------------------------------------------------------------------------------
+    _BANK_DTYPES = {"sift": np.int8, "sift_raw": np.int8, "special": np.int8, "surf": np.int8, "positions": np.float32}
+
+    def debug_view_bank(self, view, shard=0):
+        """osfm_match_debug_view_bank: a dictionary of the view's counts and of every array a matching call reads."""
+        b = capi.ViewBank()
+        capi.check(capi.lib.osfm_match_debug_view_bank(self._h, int(view), int(shard), C.byref(b)))
+        sp = b.n_special > 0
+        length = {"sift": b.n_sift_pad * 128, "sift_raw": b.n_sift_pad * 128, "sift_corr": b.n_sift_pad, "sift_raw_corr": b.n_sift_pad,
+                  "surf": b.n_surf_pad * 64, "surf_corr": b.n_surf_pad, "special": b.n_special_pad * 128,
+                  "special_corr": b.n_special_pad, "special_map": b.n_special if sp else 0, "special_slot": b.n_sift if sp else 0,
+                  "positions": max(b.n_positions, 0) * 2}
+        out = {n: np.zeros(length[n], self._BANK_DTYPES.get(n, np.int32)) for n in capi.ViewBank.ARRAYS}
+        for n, a in out.items():
+            setattr(b, n, a.ctypes.data if a.size else None)
+        capi.check(capi.lib.osfm_match_debug_view_bank(self._h, int(view), int(shard), C.byref(b)))
+        out.update({n: int(getattr(b, n)) for n in capi.ViewBank.COUNTS})
+        return out
+
+    def debug_set_view_device(self, view, sift, sift_order, surf, surf_order, positions):
+        """osfm_match_debug_set_view_device: float rows (and optional permutations) through the device hand-off."""
+        sift = np.ascontiguousarray(sift, dtype=np.float32).reshape(-1, 128)
+        surf = np.ascontiguousarray(surf, dtype=np.float32).reshape(-1, 64)
+        so = None if sift_order is None else np.ascontiguousarray(sift_order, dtype=np.int32)
+        uo = None if surf_order is None else np.ascontiguousarray(surf_order, dtype=np.int32)
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 2)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        capi.check(capi.lib.osfm_match_debug_set_view_device(self._h, int(view), ptr(sift), sift.shape[0], ptr(so), ptr(surf),
+                                                             surf.shape[0], ptr(uo), ptr(pos)))
+
     def expect_pairs(self, pairs_per_call: int):
         """The largest compute() call to come: the work arrays are sized for it at once (osfm_match_expect_pairs)."""
         capi.check(capi.lib.osfm_match_expect_pairs(self._h, C.c_int32(int(pairs_per_call))))

@@ -426,9 +426,64 @@ _list_buffers = _ListBufferPool()
 
 def match_and_build_tracks(iset, matcher="exhaustive", device=0, verify=True, timings=None, pairs=None):
     """calculateTracksUsingMVE up to (and including) the track conversion."""
+    W, H = iset.width, iset.height
+
+    def upload(m, v):
+        m.set_view(v, iset.sift[v], iset.surf[v] if iset.surf[v].shape[0] else None)
+        xy = ((iset.pos[v] + 0.5 - np.array([W / 2, H / 2])) / max(W, H)).astype(np.float32)   # feature_set.cc:42-55
+        if iset.surf[v].shape[0]:
+            xy = np.concatenate([xy, np.zeros((iset.surf[v].shape[0], 2), np.float32)])
+        if verify:
+            m.set_positions(v, xy)
+        return xy
+
+    sizes = np.array([iset.sift[v].shape[0] + iset.surf[v].shape[0] for v in range(iset.num_views)], dtype=np.int32)
+    tt, info, _ = _match_and_build(iset.num_views, upload, sizes, lambda: W, matcher, device, verify, timings, pairs, None, None)
+    return tt, info
+
+
+def tracks_from_images(images, matcher="exhaustive", device=0, verify=True, downscale_factor=1, max_image_size=6_000_000,
+                       options=None, timings=None, pairs=None):
+    """calculateTracksUsingMVE from decoded images onwards: every image (uint8 [h, w] or [h, w, 3]) goes through a
+    features.ViewFrontEnd -- the halving chain, SIFT and SURF, colours and normalised positions on the device -- and
+    from there into the matcher without the descriptors' way through the host; then matching, RANSAC-F, the tracks
+    and the reference's pixel conversion, import_width * (pos + 0.5) on BOTH axes with pos normalised by the size of
+    the feature image (matching_mve.cpp:455-466; import_width is the last view's, as the reference's imageWidth is
+    whichever view wrote it last).  options: the capi.MatchOptions to start from (geometric_verification and the
+    matcher type are set here).  Returns (TrackTable, track colours (num_tracks, 3) uint8, info)."""
+    from .features import ViewFrontEnd
+    images = [np.asarray(im) for im in images]
+    if not images:
+        raise ValueError("tracks_from_images: no images")
+    front = ViewFrontEnd(device, max(im.shape[1] for im in images), max(im.shape[0] for im in images), downscale_factor,
+                         max_image_size)
+    colors, width = [None] * len(images), [0]
+
+    def upload(m, v):
+        s = front.load(images[v])
+        m.set_view_from_front(v, front)
+        fs = front.download()
+        colors[v], width[0] = fs.colors, s.import_width
+        return fs.normalized
+
+    try:
+        tt, info, tcol = _match_and_build(len(images), upload, None, lambda: width[0], matcher, device, verify, timings, pairs,
+                                          options, colors)
+        return tt, tcol, info
+    finally:
+        front.close()
+
+
+def _match_and_build(V, upload, sizes, image_width, matcher, device, verify, timings, pairs, options, colors):
+    """The body of match_and_build_tracks with the upload of a view as a parameter: upload(m, v) sets view v of the
+    matcher (its positions too) and returns the view's normalised positions.  sizes: the features per view, or None
+    where only the uploads know them (the matching then starts when every view is there).  image_width() is asked
+    after the uploads; colors: None, or a list the uploads fill with FeatureSet::colors per view."""
     tm = timings if timings is not None else Timings()
-    V = iset.num_views
-    o = capi.default_match_options()
+    if options is not None:
+        o = capi.MatchOptions.from_buffer_copy(options)
+    else:
+        o = capi.default_match_options()
     o.geometric_verification = 1 if verify else 0
     cls = HipExhaustiveMatching if matcher == "exhaustive" else HipCascadeHashing
     import queue
@@ -437,7 +492,6 @@ def match_and_build_tracks(iset, matcher="exhaustive", device=0, verify=True, ti
     m = cls(V, device=device, options=o, copy_results=False)
     tm.setup_s = time.perf_counter() - t0
     norm = [None] * V
-    W, H = iset.width, iset.height
     # The views go up on a thread of their own (the library gives uploads their own stream and lock): the
     # first batch of pairs -- in the reference's order pair i names views up to sqrt(2 i) -- starts as soon
     # as the views it names are there, the rest of the bank follows beside the matching.
@@ -448,13 +502,7 @@ def match_and_build_tracks(iset, matcher="exhaustive", device=0, verify=True, ti
     def upload_worker():
         try:
             for v in range(V):
-                m.set_view(v, iset.sift[v], iset.surf[v] if iset.surf[v].shape[0] else None)
-                xy = ((iset.pos[v] + 0.5 - np.array([W / 2, H / 2])) / max(W, H)).astype(np.float32)   # feature_set.cc:42-55
-                if iset.surf[v].shape[0]:
-                    xy = np.concatenate([xy, np.zeros((iset.surf[v].shape[0], 2), np.float32)])
-                norm[v] = xy
-                if verify:
-                    m.set_positions(v, xy)
+                norm[v] = upload(m, v)
                 with up_cv:
                     uploaded[0] = v + 1
                     up_cv.notify_all()
@@ -476,7 +524,9 @@ def match_and_build_tracks(iset, matcher="exhaustive", device=0, verify=True, ti
     if pairs is None:
         pairs = [capi.pair_from_index(i) for i in range(V * (V - 1) // 2)]
     pf = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
-    sizes = np.array([iset.sift[v].shape[0] + iset.surf[v].shape[0] for v in range(V)], dtype=np.int32)
+    if sizes is None:
+        wait_for_views(V)
+        sizes = np.array([sum(m.view_size(v)) for v in range(V)], dtype=np.int32)
     # Matching and track building side by side: the pair list goes through the matcher in batches
     # (in pair order), and while the device works on batch k + 1 a second thread merges the lists of
     # batch k into the tracks (Tracks::compute is a sequential merge over the pairs in that order, so
@@ -568,13 +618,14 @@ def match_and_build_tracks(iset, matcher="exhaustive", device=0, verify=True, ti
     buf_thread.join()
     for b in checked_out:
         _list_buffers.release(b)
-    ids, toff, tfeat, tcol, summary = builder.finish(want_track_ids=False)      # Viewport::track_ids are not used downstream
+    all_colors = np.concatenate(colors) if colors is not None else None
+    ids, toff, tfeat, tcol, summary = builder.finish(all_colors, want_track_ids=False)      # Viewport::track_ids are not used downstream
     # tracks_s: what the job waited for after the last batch was matched (the merge of the earlier
     # batches ran beside the matching: tracks_busy_s of it in all)
     tm.tracks_s = time.perf_counter() - t0
     tm.tracks_busy_s = tracks_busy[0]
     t0 = time.perf_counter()
-    tt = TrackTable.from_mve(toff, tfeat, norm, W, V)
+    tt = TrackTable.from_mve(toff, tfeat, norm, image_width(), V)
     tm.convert_s = time.perf_counter() - t0
     info = {"num_pairs": int(pf.shape[0]), "matched_pairs": int(builder.num_pairs), "correspondences": int(builder.num_matches),
             "num_mve_tracks": int(summary.num_tracks), "invalid_mve_tracks": int(summary.num_invalid_tracks),
@@ -590,7 +641,7 @@ def match_and_build_tracks(iset, matcher="exhaustive", device=0, verify=True, ti
     closer = threading.Thread(target=m.close, daemon=True)
     closer.start()
     _background.append(closer)
-    return tt, info
+    return tt, info, tcol
 
 
 _background = []
