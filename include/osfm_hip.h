@@ -443,7 +443,12 @@ typedef struct osfm_ba_options {
      * copy of the tracks that it discards; whether to keep the returned points is the
      * caller's choice. */
     int32_t retriangulate_points;      /* 0 */
-    int32_t reserved;
+    /* Which form of the solve runs (this field was `reserved`, always 0: offset and struct size are unchanged).
+     * 0: the general form.  1: the one-workgroup form (the whole solve in one launch of one workgroup) where the
+     * problem has at most 8 cameras and at most auto_max_observations observations (osfm_ba_small_limits), else
+     * the general form.  2: the one-workgroup form; OSFM_E_ARG with more than 8 cameras.  Any other value:
+     * OSFM_E_ARG.  The two forms differ in the order of their sums only; each repeats to the bit. */
+    int32_t small_form;                /* 0 */
 } osfm_ba_options;
 
 enum {
@@ -484,6 +489,11 @@ typedef struct osfm_ba_summary {
 } osfm_ba_summary;
 
 OSFM_API int osfm_ba_options_default(osfm_ba_options *opts);
+
+/* The constants of the one-workgroup form (osfm_ba_options::small_form): the most cameras it takes, the tracks it
+ * walks per round, and the most observations at which small_form == 1 picks it (0: never).  Any pointer may be
+ * NULL. */
+OSFM_API int osfm_ba_small_limits(int32_t *max_cameras, int32_t *track_chunk, int32_t *auto_max_observations);
 
 /* ceres::Solve on the problem runBundleAdjustment builds
  * (bundle_adjustment.cpp:61-145): cam_params and points updated in place. */

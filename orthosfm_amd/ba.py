@@ -140,12 +140,25 @@ class FlatProblem:
         return p
 
 
-def default_options(**kw) -> capi.BaOptions:
+SMALL_FORM_GENERAL, SMALL_FORM_AUTO, SMALL_FORM_ONE_WORKGROUP = 0, 1, 2
+
+
+def default_options(small_form: int = SMALL_FORM_GENERAL, **kw) -> capi.BaOptions:
+    """osfm_ba_options_default with fields replaced.  small_form: 0 the general form, 1 the one-workgroup form where
+    the problem is small enough (small_limits()), 2 the one-workgroup form or OsfmError(E_ARG)."""
     o = capi.BaOptions()
     capi.check(capi.lib.osfm_ba_options_default(C.byref(o)))
+    o.small_form = small_form
     for k, v in kw.items():
         setattr(o, k, v)
     return o
+
+
+def small_limits():
+    """osfm_ba_small_limits: (max_cameras, track_chunk, auto_max_observations) of the one-workgroup form."""
+    v = [C.c_int32() for _ in range(3)]
+    capi.check(capi.lib.osfm_ba_small_limits(*[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
 
 
 def solve(problem: FlatProblem, options: capi.BaOptions | None = None, **kw) -> capi.BaSummary:

@@ -100,7 +100,7 @@ class BaOptions(C.Structure):
                 ("min_lm_diagonal", C.c_double), ("max_lm_diagonal", C.c_double),
                 ("jacobi_scaling", C.c_int32), ("max_consecutive_invalid_steps", C.c_int32),
                 ("device", C.c_int32), ("verbose", C.c_int32),
-                ("retriangulate_points", C.c_int32), ("reserved", C.c_int32)]
+                ("retriangulate_points", C.c_int32), ("small_form", C.c_int32)]
 
 
 class TracksSummary(C.Structure):
@@ -227,7 +227,7 @@ EXPORTS = [
     "osfm_ransac_options_default", "osfm_ransac_fundamental",
     "osfm_match_pair", "osfm_match_pair_lowres", "osfm_match_twoway", "osfm_match_all",
     "osfm_pair_from_index", "osfm_match_get_stats", "osfm_match_get_shard_stats", "osfm_match_get_cascade_hashes",
-    "osfm_ba_options_default", "osfm_ba_solve", "osfm_ba_reprojection_errors",
+    "osfm_ba_options_default", "osfm_ba_small_limits", "osfm_ba_solve", "osfm_ba_reprojection_errors",
     "osfm_ba_triangulate",
     "osfm_nn_distances", "osfm_filter_outlier_tracks", "osfm_filter_reprojection",
     "osfm_scene_create", "osfm_scene_destroy", "osfm_scene_set_flags", "osfm_scene_align_views", "osfm_scene_set_cameras", "osfm_scene_get_cameras",
@@ -289,6 +289,7 @@ lib.osfm_match_set_view_from_front.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
 lib.osfm_match_debug_view_bank.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(ViewBank)]
 lib.osfm_match_debug_set_view_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                  C.c_void_p, C.c_void_p]
+lib.osfm_ba_small_limits.argtypes = [C.POINTER(C.c_int32)] * 3
 lib.osfm_ba_debug_cholesky_solve.restype = C.c_int
 lib.osfm_ba_debug_cholesky_solve.argtypes = [C.c_int, C.c_int, _f64p, _f64p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, _f64p, _i32p, _i32p]

@@ -317,7 +317,15 @@ int osfm_ba_options_default(osfm_ba_options *o)
     o->device = 0;
     o->verbose = 0;
     o->retriangulate_points = 0;
-    o->reserved = 0;
+    o->small_form = 0;
+    return OSFM_OK;
+}
+
+int osfm_ba_small_limits(int32_t *max_cameras, int32_t *track_chunk, int32_t *auto_max_observations)
+{
+    if (max_cameras) *max_cameras = kSmallMaxCams;
+    if (track_chunk) *track_chunk = kSmallTrackChunk;
+    if (auto_max_observations) *auto_max_observations = kSmallAutoMaxObs;
     return OSFM_OK;
 }
 
@@ -330,6 +338,7 @@ static int ba_solve_host(const osfm_ba_problem *p, const osfm_ba_options *opt, o
     OSFM_RETURN_IF(validate_header(p, "ba_solve"));
     osfm_ba_options o;
     if (opt) o = *opt; else osfm_ba_options_default(&o);
+    OSFM_RETURN_IF(check_small_form(o, p->num_cameras, cap != nullptr, cap ? "ba_debug_linearization" : "ba_solve"));
     // The sweep over the caller's observations (range / order / one-observation-per-camera checks, the points'
     // observation counts, the copy of the start points) takes as long as queueing the uploads does (0.4 ms each for
     // BASELINE config 4: pageable arrays are staged by the calling thread): for problems of that size it runs on a

@@ -79,6 +79,92 @@ struct LmScratch {
     int32_t reset_n, reset_N;    // identity on the padding diagonal from reset_n on); null otherwise
 };
 
+// The decisions of TrustRegionMinimizer / LevenbergMarquardtStrategy, by one thread from the reduced sums: what
+// ba_lm_decide / ba_lm_post (ba_kernels.hip) and the one-workgroup form (ba_small.hip) both take.
+// After the candidate of an iteration has been evaluated: step validity, the parameter / function tolerance tests,
+// accept or reject, the new radius, and what the linearisation that follows has to do.
+__device__ __forceinline__ void
+lm_decide_logic(LmDev *lm, const LmParams &prm, const LmScratch &sc, bool solved, double mcc, double sn, double xn,
+    double cand)
+{
+    const int info = *sc.chol_info;
+    *sc.chol_info = 0;
+    const double step_norm = sqrt(sn), x_norm = sqrt(xn);
+    lm->model_cost_change = mcc; lm->step_norm = step_norm; lm->x_norm = x_norm; lm->cand_cost = cand;
+    const bool solve_ok = solved && info == 0 && isfinite(mcc) && isfinite(step_norm);
+    const bool step_valid = solve_ok && mcc > 0.0;
+    if (!step_valid) {
+        // HandleInvalidStep -> LevenbergMarquardtStrategy::StepIsInvalid
+        if (++lm->invalid_steps >= prm.max_invalid_steps) { lm->term = OSFM_BA_FAILURE; lm->stop = 1; return; }
+        lm->radius = lm->radius / lm->decrease_factor; lm->decrease_factor *= 2.0;
+        lm->num_unsuccess++;
+        lm->update_diag = 0; lm->want_gradient = 0;
+        return;
+    }
+    lm->invalid_steps = 0;
+    if (!isfinite(cand)) cand = 1.7976931348623157e308;
+    // ParameterToleranceReached / FunctionToleranceReached
+    if (step_norm <= prm.parameter_tolerance * (x_norm + prm.parameter_tolerance)) { lm->term = OSFM_BA_CONVERGENCE_PARAMETER; lm->stop = 1; return; }
+    const double cost_change = lm->x_cost - cand;
+    if (fabs(cost_change) <= prm.function_tolerance * lm->x_cost) { lm->term = OSFM_BA_CONVERGENCE_FUNCTION; lm->stop = 1; return; }
+    const double relative_decrease = cost_change / mcc;
+    if (relative_decrease > prm.min_relative_decrease) {
+        // HandleSuccessfulStep + LevenbergMarquardtStrategy::StepAccepted
+        lm->cur ^= 1;
+        const double t = 2.0 * relative_decrease - 1.0;
+        lm->radius = fmin(prm.max_radius, lm->radius / fmax(1.0 / 3.0, 1.0 - t * t * t));
+        lm->decrease_factor = 2.0;
+        lm->num_success++;
+        lm->last_successful = 1;
+        lm->update_diag = 1; lm->want_gradient = 1;
+    } else {
+        // LevenbergMarquardtStrategy::StepRejected
+        lm->radius = lm->radius / lm->decrease_factor; lm->decrease_factor *= 2.0;
+        lm->num_unsuccess++;
+        lm->update_diag = 0; lm->want_gradient = 0;
+    }
+}
+
+// After a linearisation: cost / gradient norm of a new iterate, the not-positive-definite
+// flag, then FinalizeIterationAndCheckIfMinimizerCanContinue for the iteration that follows.
+__device__ __forceinline__ void
+lm_post_logic(LmDev *lm, const LmParams &prm, int initial, double cost, double gp, double bad, double gc)
+{
+    if (lm->want_gradient) { lm->x_cost = cost; lm->grad_max = fmax(gp, gc); }
+    lm->lin_failed = bad != 0.0 ? 1 : 0;
+    if (initial) {
+        lm->initial_cost = cost;
+        if (!isfinite(cost)) { lm->nonfinite = 1; lm->term = OSFM_BA_FAILURE; lm->stop = 1; return; }
+        if (lm->grad_max <= prm.gradient_tolerance) { lm->term = OSFM_BA_CONVERGENCE_GRADIENT; lm->stop = 1; return; }
+    }
+    // the LM diagonal is refreshed by the linearisation that follows an accepted step only
+    lm->update_diag = 0; lm->want_gradient = 0;
+    if (lm->iteration >= prm.max_iterations) { lm->term = OSFM_BA_NO_CONVERGENCE; lm->stop = 1; return; }
+    if (lm->last_successful && lm->grad_max <= prm.gradient_tolerance) { lm->term = OSFM_BA_CONVERGENCE_GRADIENT; lm->stop = 1; return; }
+    if (lm->radius <= prm.min_radius) { lm->term = OSFM_BA_CONVERGENCE_TRUST_REGION; lm->stop = 1; return; }
+    lm->iteration++;
+    lm->last_successful = 0;
+}
+
+// ---- ba_small.hip: the whole solve of a problem of at most kSmallMaxCams cameras in ONE launch of ONE workgroup
+// ("The one-workgroup form").  Tracks are walked kSmallTrackChunk at a time (a thread each), so the
+// numbers of points and observations have no limit of their own.  kSmallAutoMaxObs: the largest number of
+// observations at which osfm_ba_options::small_form == 1 picks this form -- the largest O of the 3-camera sweep of
+// tools/small_ba_timing.py at which this form's 95th percentile of solve_ms lay below the general form's 5th
+// (profiles/small_ba_timing.txt: one chunk of tracks; from two chunks on the general form wins).
+constexpr int kSmallMaxCams = 8, kSmallTrackChunk = 256, kSmallAutoMaxObs = 768;
+struct SmallBaArgs {
+    LmParams prm;
+    double radius0, min_diag, max_diag;
+    int32_t jacobi_scaling, pad0;
+    double *obsrec;           // [O][kObsRec] the records of the last linearisation (global memory: L2 at these sizes)
+    double *diag_p, *vinv, *ge, *scale_p;     // [3M], [9M], [3M], [3M]
+    LmDev *lm;                // the state the solve leaves (ba_solve_core's `fin`)
+    long long *stamps;        // [3] wall_clock64 (100 MHz) at the start, in front of the first iteration, at the end
+};
+// d: a finished DeviceProblem's BaDev with cams2 / points2 set, C <= kSmallMaxCams, nc <= 6 C in the cameras' own order
+void launch_small_ba(const BaDev &d, const SmallBaArgs &a, hipStream_t s);
+
 // What the last workgroup of a launch needs to run the LM control in its tail (ba_lm_decide behind the back pass,
 // ba_lm_post behind the pair pass) instead of a launch of one workgroup each: 6-14 us of kernel plus a launch gap,
 // twice per iteration.  Every workgroup leaves its partials write-through and takes a ticket; the one that takes

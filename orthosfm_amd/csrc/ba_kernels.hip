@@ -170,47 +170,7 @@ __device__ __forceinline__ void publish_state(const LmDev *lm, LmDev *host_out)
     if (host_out) *host_out = *lm;
 }
 
-__device__ __forceinline__ void
-lm_decide_logic(LmDev *lm, const LmParams &prm, const LmScratch &sc, bool solved, double mcc, double sn, double xn,
-    double cand)
-{
-    const int info = *sc.chol_info;
-    *sc.chol_info = 0;
-    const double step_norm = sqrt(sn), x_norm = sqrt(xn);
-    lm->model_cost_change = mcc; lm->step_norm = step_norm; lm->x_norm = x_norm; lm->cand_cost = cand;
-    const bool solve_ok = solved && info == 0 && isfinite(mcc) && isfinite(step_norm);
-    const bool step_valid = solve_ok && mcc > 0.0;
-    if (!step_valid) {
-        // HandleInvalidStep -> LevenbergMarquardtStrategy::StepIsInvalid
-        if (++lm->invalid_steps >= prm.max_invalid_steps) { lm->term = OSFM_BA_FAILURE; lm->stop = 1; return; }
-        lm->radius = lm->radius / lm->decrease_factor; lm->decrease_factor *= 2.0;
-        lm->num_unsuccess++;
-        lm->update_diag = 0; lm->want_gradient = 0;
-        return;
-    }
-    lm->invalid_steps = 0;
-    if (!isfinite(cand)) cand = 1.7976931348623157e308;
-    // ParameterToleranceReached / FunctionToleranceReached
-    if (step_norm <= prm.parameter_tolerance * (x_norm + prm.parameter_tolerance)) { lm->term = OSFM_BA_CONVERGENCE_PARAMETER; lm->stop = 1; return; }
-    const double cost_change = lm->x_cost - cand;
-    if (fabs(cost_change) <= prm.function_tolerance * lm->x_cost) { lm->term = OSFM_BA_CONVERGENCE_FUNCTION; lm->stop = 1; return; }
-    const double relative_decrease = cost_change / mcc;
-    if (relative_decrease > prm.min_relative_decrease) {
-        // HandleSuccessfulStep + LevenbergMarquardtStrategy::StepAccepted
-        lm->cur ^= 1;
-        const double t = 2.0 * relative_decrease - 1.0;
-        lm->radius = fmin(prm.max_radius, lm->radius / fmax(1.0 / 3.0, 1.0 - t * t * t));
-        lm->decrease_factor = 2.0;
-        lm->num_success++;
-        lm->last_successful = 1;
-        lm->update_diag = 1; lm->want_gradient = 1;
-    } else {
-        // LevenbergMarquardtStrategy::StepRejected
-        lm->radius = lm->radius / lm->decrease_factor; lm->decrease_factor *= 2.0;
-        lm->num_unsuccess++;
-        lm->update_diag = 0; lm->want_gradient = 0;
-    }
-}
+// (the decisions themselves, lm_decide_logic / lm_post_logic: ba_kernels.h -- the one-workgroup form takes the same)
 
 // One workgroup of 256 threads (a kernel of its own, or the last workgroup of the back pass: SC1)
 template <bool SC1>
@@ -251,27 +211,6 @@ ba_lm_decide_kernel(LmDev *lm, LmParams prm, LmScratch sc, LmDev *host_out)
 {
     __shared__ double sh[256];
     lm_decide_block<false>(lm, prm, sc, host_out, sh);
-}
-
-// After a linearisation: cost / gradient norm of a new iterate, the not-positive-definite
-// flag, then FinalizeIterationAndCheckIfMinimizerCanContinue for the iteration that follows.
-__device__ __forceinline__ void
-lm_post_logic(LmDev *lm, const LmParams &prm, int initial, double cost, double gp, double bad, double gc)
-{
-    if (lm->want_gradient) { lm->x_cost = cost; lm->grad_max = fmax(gp, gc); }
-    lm->lin_failed = bad != 0.0 ? 1 : 0;
-    if (initial) {
-        lm->initial_cost = cost;
-        if (!isfinite(cost)) { lm->nonfinite = 1; lm->term = OSFM_BA_FAILURE; lm->stop = 1; return; }
-        if (lm->grad_max <= prm.gradient_tolerance) { lm->term = OSFM_BA_CONVERGENCE_GRADIENT; lm->stop = 1; return; }
-    }
-    // the LM diagonal is refreshed by the linearisation that follows an accepted step only
-    lm->update_diag = 0; lm->want_gradient = 0;
-    if (lm->iteration >= prm.max_iterations) { lm->term = OSFM_BA_NO_CONVERGENCE; lm->stop = 1; return; }
-    if (lm->last_successful && lm->grad_max <= prm.gradient_tolerance) { lm->term = OSFM_BA_CONVERGENCE_GRADIENT; lm->stop = 1; return; }
-    if (lm->radius <= prm.min_radius) { lm->term = OSFM_BA_CONVERGENCE_TRUST_REGION; lm->stop = 1; return; }
-    lm->iteration++;
-    lm->last_successful = 0;
 }
 
 // One workgroup of 256 threads (a kernel of its own, or the last workgroup of the pair pass: GMAX_SC1 -- the

@@ -78,8 +78,14 @@ int finish_device_problem(int model, int C, int M, int O, int nc, double huber, 
 // leaves as it was.  pair_bound: an upper bound of the Schur pair entries (sum of squared track lengths), refused beyond
 // 2^31 - 1.  On return *cur names the buffer pair (cams[cur], points[cur]) that holds the result; the stream is
 // synchronised.  cap (test hook osfm_ba_debug_linearization; null in every solve): copies of the first iteration
+// o.small_form (osfm_hip.h) picks between the general form and the one-workgroup form (ba_small.hip) here, so
+// every caller honours it; both leave the same things behind.
 int ba_solve_core(const DeviceProblem &D, const osfm_ba_options &o, StreamLease &sg, int64_t pair_bound, osfm_ba_summary *sum,
     int *cur, osfm_ba_lin_capture *cap = nullptr);
+// osfm_ba_options::small_form against a problem of num_cameras cameras (capture: osfm_ba_debug_linearization):
+// OSFM_E_ARG for a value that is none of 0, 1, 2 and for 2 where the one-workgroup form cannot run.  The entry
+// points call it before they queue anything; ba_solve_core calls it too.
+int check_small_form(const osfm_ba_options &o, int num_cameras, bool capture, const char *what);
 
 // The dense Cholesky's buffers for a system of span unknowns, padded to N: S with the right-hand side in row N, the
 // factor, Ldiag, the solution y; for the one-launch form (flow) its hand-off flags, zeroed here once, and mailbox

@@ -407,11 +407,77 @@ int fill_summary(const LmDev &fin, const KernelTimer &t, Clock::time_point t_loo
     return OSFM_OK;
 }
 
+// The one-workgroup form (ba_small.hip): no observation windows, pair lists, elimination order or Cholesky buffers --
+// the per-observation records and per-point blocks, one launch, one read of the state it leaves.  The summary's
+// per-kernel-family times and list / order fields stay 0; lm_loop_ms is the device's own time between the first
+// linearisation and the end of the launch.
+int small_solve(const DeviceProblem &D, const osfm_ba_options &o, StreamLease &sg, osfm_ba_summary *sum, int *cur_out)
+{
+    const auto t_begin = Clock::now();
+    hipStream_t s = sg.s;
+    BaDev d = D.dev;
+    const size_t M = (size_t)d.M, O = (size_t)d.O;
+    if (d.nc > 6 * kSmallMaxCams) { set_error("ba_solve: %d camera unknowns in the one-workgroup form", d.nc); return OSFM_E_ARG; }
+    DevArray obsrec, diag_p, vinv, ge, scale_p, state;
+    OSFM_RETURN_IF(obsrec.alloc(O * kObsRec * 8));
+    OSFM_RETURN_IF(diag_p.alloc(3 * M * 8));
+    OSFM_RETURN_IF(vinv.alloc(9 * M * 8));
+    OSFM_RETURN_IF(ge.alloc(3 * M * 8));
+    OSFM_RETURN_IF(scale_p.alloc(3 * M * 8));
+    constexpr size_t kStampsAt = (sizeof(LmDev) + 15) / 16 * 16, kStateBytes = kStampsAt + 3 * sizeof(long long);
+    OSFM_RETURN_IF(state.alloc(kStateBytes));
+    OSFM_RETURN_IF(sg.set->ensure_pinned(kStateBytes));
+    d.cams2[0] = D.cams[0].as<double>(); d.cams2[1] = D.cams[1].as<double>();
+    d.points2[0] = D.points[0].as<double>(); d.points2[1] = D.points[1].as<double>();
+    SmallBaArgs a;
+    memset(&a, 0, sizeof(a));
+    a.prm = {o.function_tolerance, o.gradient_tolerance, o.parameter_tolerance, o.min_relative_decrease, o.max_trust_region_radius,
+             o.min_trust_region_radius, o.max_num_iterations, o.max_consecutive_invalid_steps};
+    a.radius0 = o.initial_trust_region_radius; a.min_diag = o.min_lm_diagonal; a.max_diag = o.max_lm_diagonal;
+    a.jacobi_scaling = o.jacobi_scaling ? 1 : 0;
+    a.obsrec = obsrec.as<double>(); a.diag_p = diag_p.as<double>(); a.vinv = vinv.as<double>(); a.ge = ge.as<double>();
+    a.scale_p = scale_p.as<double>();
+    a.lm = state.as<LmDev>(); a.stamps = reinterpret_cast<long long *>(state.as<char>() + kStampsAt);
+    launch_small_ba(d, a, s);
+    OSFM_HIP_CHECK(hipGetLastError());
+    char *h = static_cast<char *>(sg.set->pinned);
+    OSFM_HIP_CHECK(hipMemcpyAsync(h, state.ptr, kStateBytes, hipMemcpyDeviceToHost, s));
+    OSFM_HIP_CHECK(hipStreamSynchronize(s));
+    LmDev fin;
+    long long stamps[3];
+    memcpy(&fin, h, sizeof(fin));
+    memcpy(stamps, h + kStampsAt, sizeof(stamps));
+    if (fin.nonfinite) { set_error("ba_solve: non-finite initial cost"); return OSFM_E_NUMERIC; }
+    sum->lm_loop_ms = (double)(stamps[2] - stamps[1]) * 1e-5;       // 100 MHz
+    sum->initial_cost = fin.initial_cost; sum->final_cost = fin.x_cost;
+    sum->num_successful_steps = fin.num_success; sum->num_unsuccessful_steps = fin.num_unsuccess;
+    sum->num_iterations = fin.iteration; sum->termination = fin.term;
+    sum->linearizations = fin.num_success + fin.num_unsuccess + 1;
+    lap(o.verbose, t_begin, "  one-workgroup solve");
+    *cur_out = fin.cur;
+    return OSFM_OK;
+}
+
 }  // namespace
+
+int check_small_form(const osfm_ba_options &o, int num_cameras, bool capture, const char *what)
+{
+    if (o.small_form < 0 || o.small_form > 2) { set_error("%s: small_form %d (0: general form, 1: by size, 2: one-workgroup form)", what, o.small_form); return OSFM_E_ARG; }
+    if (o.small_form != 2) return OSFM_OK;
+    if (capture) { set_error("%s: the capture is of the general form, small_form is 2", what); return OSFM_E_ARG; }
+    if (num_cameras > kSmallMaxCams) {
+        set_error("%s: small_form 2 with %d cameras: the one-workgroup form takes at most %d", what, num_cameras, kSmallMaxCams);
+        return OSFM_E_ARG;
+    }
+    return OSFM_OK;
+}
 
 int ba_solve_core(const DeviceProblem &D, const osfm_ba_options &o, StreamLease &sg, int64_t pair_bound, osfm_ba_summary *sum,
     int *cur_out, osfm_ba_lin_capture *cap)
 {
+    OSFM_RETURN_IF(check_small_form(o, D.dev.C, cap != nullptr, "ba_solve"));
+    if (!cap && (o.small_form == 2 || (o.small_form == 1 && D.dev.C <= kSmallMaxCams && D.dev.O <= kSmallAutoMaxObs)))
+        return small_solve(D, o, sg, sum, cur_out);
     const auto t_begin = Clock::now();
     const Switches sw{};
     hipStream_t s = sg.s;

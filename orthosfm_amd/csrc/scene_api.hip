@@ -883,6 +883,7 @@ int osfm_scene_local_adjustment(osfm_scene *sc, int n, const int32_t *views, dou
     memset(sum, 0, sizeof(*sum));
     osfm_ba_options o;
     if (opt) o = *opt; else osfm_ba_options_default(&o);
+    OSFM_RETURN_IF(check_small_form(o, n, false, "scene_local_adjustment"));
     std::lock_guard<std::mutex> lock(sc->mu);
     OSFM_RETURN_IF(select_device(sc->device));
     const auto t_begin = std::chrono::steady_clock::now();
@@ -934,6 +935,7 @@ int osfm_scene_global_adjustment(osfm_scene *sc, const osfm_ba_options *opt, osf
     osfm_ba_options o;
     if (opt) o = *opt; else osfm_ba_options_default(&o);
     std::lock_guard<std::mutex> lock(sc->mu);
+    OSFM_RETURN_IF(check_small_form(o, (int)sc->aligned.size(), false, "scene_global_adjustment"));
     OSFM_RETURN_IF(select_device(sc->device));
     const auto t_begin = std::chrono::steady_clock::now();
     StreamLease sg;

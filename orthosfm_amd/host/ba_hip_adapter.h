@@ -50,8 +50,9 @@ std::vector<Track> filter_tracks_to_available_cameras(std::vector<CameraPtr> con
 // constructible from four doubles that setPoint accepts).
 template <class QuatCamera, class EulerCamera, class Vec4, class CameraPtr, class Track, class AlgorithmPtr>
 void runBundleAdjustment(std::vector<CameraPtr>& cameras, std::vector<Track>& tracks,
-    AlgorithmPtr const& algorithm, bool optimizePoints, bool retriangulatePoints, int device = 0)
+    AlgorithmPtr const& algorithm, bool optimizePoints, bool retriangulatePoints, int device = 0, int smallForm = 0)
 {
+    // smallForm: osfm_ba_options::small_form (0 the general form, 1 by size, 2 the one-workgroup form: at most 8 cameras)
     const bool quat = algorithm->getName() == "Ortho Quaternion Reconstruction";
     std::map<unsigned int, int> viewToCam;                                       // :54-57 (insert keeps the first)
     for (int i = 0; i < (int)cameras.size(); ++i)
@@ -119,6 +120,7 @@ void runBundleAdjustment(std::vector<CameraPtr>& cameras, std::vector<Track>& tr
     o.optimize_points = optimizePoints ? 1 : 0;
     o.retriangulate_points = retriangulatePoints ? 1 : 0;
     o.device = device;
+    o.small_form = smallForm;
     osfm_ba_summary s;
     if (osfm_ba_solve(&p, &o, &s) != OSFM_OK)
         throw std::runtime_error(std::string("osfm: ") + osfm_last_error());

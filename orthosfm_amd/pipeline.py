@@ -656,13 +656,17 @@ def join_background():
 def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2.0, off_perturb=0.01,
                         seed=7, timings=None, capture=(), max_groups=None, verbose=False, view_ids=None,
                         euler_dof=4, check_incremental=False, use_scene=True, initial_alignment="perturbed",
-                        alignments=None):
+                        alignments=None, local_solver="general"):
     """runPoseEstimation (reconstruct.cpp:174-295) on the track table.  initial_alignment: "perturbed" or "tk" (see
     the module docstring); with "tk", group_id is the group's ordinal, seed the sampler's seed, and the groups'
     tk.Alignment records are appended to `alignments` (a list, if given).  use_scene: the table lives on the device
     for the whole loop (osfm_scene_*: every step selects its observations there); False: every step flattens its
     tracks on the host and goes through the per-call entries of the C ABI (what a caller without the scene does;
-    the two forms produce the same cameras, flags and points to the bit: tests/test_e2e_gpu.py)."""
+    the two forms produce the same cameras, flags and points to the bit: tests/test_e2e_gpu.py).  local_solver:
+    "general", or "small": every camera group's local adjustment in the one-workgroup form (small_form=2 on its
+    options; the global adjustments keep the general form)."""
+    if local_solver not in ("general", "small"):
+        raise ValueError(f"local_solver {local_solver!r}: 'general' or 'small'")
     if initial_alignment not in ("perturbed", "tk"):
         raise ValueError(f"initial_alignment {initial_alignment!r}: 'perturbed' or 'tk'")
     use_tk = initial_alignment == "tk"
@@ -691,7 +695,8 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
     is_aligned = np.zeros(V, dtype=bool)
     calls, captured = [], {}
     opt = B.default_options(device=device)
-    opt_local = B.default_options(device=device, retriangulate_points=1)
+    opt_local = B.default_options(device=device, retriangulate_points=1,
+                                  small_form=B.SMALL_FORM_ONE_WORKGROUP if local_solver == "small" else B.SMALL_FORM_GENERAL)
     scene = None
     if use_scene and not capture:
         from .scene import Scene
@@ -1012,11 +1017,12 @@ def _global_ba(tt, model, cams, const, aligned, W, H, V, solve, kind, opt, tm):
 
 def reconstruct(iset, solver=0, matcher="exhaustive", device=0, verify=True, rot_perturb_deg=2.0,
                 off_perturb=0.01, seed=7, capture=(), max_groups=None, verbose=False,
-                check_incremental=False, use_scene=True, initial_alignment="perturbed") -> Result:
+                check_incremental=False, use_scene=True, initial_alignment="perturbed", local_solver="general") -> Result:
     """orthosfm::reconstruct from the views' descriptors on: one wall clock over matching,
     track building, group ordering and the incremental pose estimation.
     solver 0: quaternion cameras (ORTHO_QUATERNION); 1..3: Euler cameras with that many
-    free angle blocks (3 = ORTHO_EULER_ALL_DOF: phi, theta, roll and the offsets)."""
+    free angle blocks (3 = ORTHO_EULER_ALL_DOF: phi, theta, roll and the offsets).
+    local_solver: run_pose_estimation's."""
     tm = Timings()
     t_all = time.perf_counter()
     tt, info = match_and_build_tracks(iset, matcher, device, verify, tm)
@@ -1025,7 +1031,7 @@ def reconstruct(iset, solver=0, matcher="exhaustive", device=0, verify=True, rot
     cams, aligned, groups, calls, captured = run_pose_estimation(
         tt, iset, model, device, rot_perturb_deg, off_perturb, seed, tm, capture, max_groups, verbose,
         euler_dof=euler_dof_of_solver(solver), check_incremental=check_incremental, use_scene=use_scene,
-        initial_alignment=initial_alignment, alignments=alignments)
+        initial_alignment=initial_alignment, alignments=alignments, local_solver=local_solver)
     join_background()            # inside the clock: the matcher's memory is back when the job is done
     tm.total_s = time.perf_counter() - t_all
     info.pop("match_stats", None)
