@@ -1,4 +1,4 @@
-// What the matcher's hand-off (match_api.hip) sees of a view front end (view_api.hip).  Not part of the C ABI.
+// What the matcher's hand-off (match_views.hip) sees of a view front end (view_api.hip).  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
