@@ -619,7 +619,8 @@ OSFM_API int osfm_scene_set_cameras(osfm_scene *s, int n, const int32_t *views, 
 /* the aligned cameras in the order they joined (views / params may be NULL) */
 OSFM_API int osfm_scene_get_cameras(osfm_scene *s, int capacity, int32_t *views, double *params, int32_t *num_cameras);
 /* algorithm->triangulateTracks(alignedCameras, tracks, true) (triangulation.cpp:44-93): every alive track with two or
- * more rays under the aligned cameras gets its intersection, the others lose their point.  new_views != NULL: only
+ * more rays under the aligned cameras gets its intersection, the other alive tracks lose their point (a dead track is
+ * in no list of the reference: it keeps what it has in either kind of pass).  new_views != NULL: only
  * the tracks those views see are redone -- identical to the full pass as long as the other cameras have not moved
  * since the last one; check_full != 0 repeats the pass in full and counts the tracks that differ (*mismatches). */
 OSFM_API int osfm_scene_triangulate(osfm_scene *s, int num_new_views, const int32_t *new_views, int check_full, int32_t *mismatches);

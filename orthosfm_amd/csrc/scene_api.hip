@@ -15,8 +15,11 @@
 // global round ~5 % of a large job's table is alive (200 views: 3.2 M features, 500 views: 8 M).  Maps back to the
 // caller's numbering serve osfm_scene_download / osfm_scene_set_flags.
 //
-// Semantics are those of orthosfm_amd/pipeline.py's per-call form (which stays, behind use_scene = False, and is
-// what tests/test_e2e_gpu.py compares this against bit for bit): see the entry points below.
+// What holds the semantics: tests/scene_model.py, the scene as plain host state written track by track from the
+// reference's text (outlier_filtering.cpp:127-192, triangulation.cpp:76-91, bundle_adjustment.cpp:86-123), and
+// tests/test_scene_steps_gpu.py, which holds every entry below to that model after every step on the tables of
+// tests/scene_cases.py.  orthosfm_amd/pipeline.py's per-call form stays behind use_scene = False;
+// tests/test_e2e_gpu.py compares a whole reconstruction on the scene with it bit for bit.
 #include <hipcub/hipcub.hpp>
 
 #include <chrono>
@@ -155,14 +158,15 @@ __global__ void scene_pair_bound_kernel(int M, const int32_t *__restrict__ pt_st
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(out, v);
 }
 
-// triangulation results back into the scene: tracks of the mask (all tracks when clear_all) lose their point, the
-// valid intersections set it (triangulation.cpp:76-91)
-__global__ void scene_store_points_kernel(int T, const uint8_t *__restrict__ tmask, int clear_all, const int32_t *__restrict__ tflag,
-    const int32_t *__restrict__ tslot, const uint8_t *__restrict__ valid, const double *__restrict__ pts,
-    uint8_t *__restrict__ has_point, double *__restrict__ point)
+// triangulation results back into the scene: alive tracks of the mask (all alive tracks when clear_all) lose their
+// point, the valid intersections set it (triangulation.cpp:76-91).  A dead track is not in the reference's list: it
+// keeps what it has in a full pass as in an incremental one (which never touches it), so that the two agree on it.
+__global__ void scene_store_points_kernel(int T, const uint8_t *__restrict__ tmask, int clear_all, const uint8_t *__restrict__ alive_t,
+    const int32_t *__restrict__ tflag, const int32_t *__restrict__ tslot, const uint8_t *__restrict__ valid,
+    const double *__restrict__ pts, uint8_t *__restrict__ has_point, double *__restrict__ point)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
+    if (t >= T || !alive_t[t]) return;
     if (!clear_all && !(tmask && tmask[t])) return;
     bool hp = false;
     if (tflag[t]) {
@@ -411,8 +415,8 @@ int triangulate_pass(osfm_scene *sc, const uint8_t *tmask, bool clear_all, uint8
         OSFM_HIP_CHECK(hipMemcpyAsync(P.D.points[1].ptr, P.D.points[0].ptr, (size_t)P.M * 32, hipMemcpyDeviceToDevice, s));
         launch_triangulate(P.D.dev, P.D.points[1].as<double>(), valid.as<uint8_t>(), s);
     }
-    hipLaunchKernelGGL(scene_store_points_kernel, dim3(blocks_for(T)), dim3(kThreads), 0, s, T, tmask, clear_all ? 1 : 0, tflag,
-        sc->tslot.as<int32_t>(), valid.as<uint8_t>(), P.D.points[1].as<double>(), hp_out, pt_out);
+    hipLaunchKernelGGL(scene_store_points_kernel, dim3(blocks_for(T)), dim3(kThreads), 0, s, T, tmask, clear_all ? 1 : 0,
+        sc->alive_t.as<uint8_t>(), tflag, sc->tslot.as<int32_t>(), valid.as<uint8_t>(), P.D.points[1].as<double>(), hp_out, pt_out);
     OSFM_HIP_CHECK(hipGetLastError());
     OSFM_HIP_CHECK(hipStreamSynchronize(s));
     return OSFM_OK;
@@ -848,6 +852,8 @@ int osfm_scene_triangulate(osfm_scene *sc, int num_new_views, const int32_t *new
     }
     OSFM_RETURN_IF(triangulate_pass(sc, tmask, !incremental, sc->has_point.as<uint8_t>(), sc->point.as<double>(), s));
     if (incremental && check_full) {
+        // (the full pass leaves the dead tracks' entries alone: they start from the scene's)
+        OSFM_HIP_CHECK(hipMemcpyAsync(sc->tmp_hp.ptr, sc->has_point.ptr, (size_t)sc->T, hipMemcpyDeviceToDevice, s));
         OSFM_HIP_CHECK(hipMemcpyAsync(sc->tmp_point.ptr, sc->point.ptr, (size_t)sc->T * 32, hipMemcpyDeviceToDevice, s));
         OSFM_RETURN_IF(triangulate_pass(sc, nullptr, true, sc->tmp_hp.as<uint8_t>(), sc->tmp_point.as<double>(), s));
         int32_t *c = sc->counters.as<int32_t>();

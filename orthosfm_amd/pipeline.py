@@ -788,7 +788,8 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
     def triangulate_all(new_views=None):
         """algorithm->triangulateTracks(alignedCameras, tracks, true): every track with two
         or more rays under the aligned cameras gets its intersection, the others lose their
-        point (triangulation.cpp:76-91)."""
+        point (triangulation.cpp:76-91).  A dead track is not in the reference's list: it keeps
+        what it has, in a full pass as in an incremental one."""
         t0 = time.perf_counter()
         subset = None
         if not tri["full"] and new_views is not None:
@@ -796,7 +797,7 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
             subset = np.unique(tt.track_of[idx]).astype(np.int64)
         uniq, valid, pts = _triangulate(subset)
         if subset is None:
-            tt.has_point[:] = False
+            tt.has_point[tt.alive_t] = False
         else:
             tt.has_point[subset] = False
         ok = uniq[valid]
@@ -805,7 +806,7 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
         if check_incremental and subset is not None:
             hp, pt = tt.has_point.copy(), tt.point.copy()
             uniq, valid, pts = _triangulate(None)
-            full_hp = np.zeros_like(hp)
+            full_hp = hp & ~tt.alive_t
             full_hp[uniq[valid]] = True
             assert np.array_equal(full_hp, hp) and np.array_equal(pts[valid], pt[uniq[valid]]), "incremental triangulation"
         tri["full"] = False
