@@ -40,7 +40,7 @@ OSFM_API const char *osfm_last_error(void);
  * adapters (the headers under orthosfm_amd/host) and the Python mirror compare this with their own OSFM_ABI_VERSION at load time.
  * 100: rounds 1-3; 101: osfm_ba_summary.flow_fallbacks, osfm_match_stats.surf_*; 102: one observation per camera
  * and point enforced, osfm_scene_set_cameras,
- * osfm_ba_summary.order_arcs / chain_blocks*.  New entries and new structs (the view front end) leave it alone:
+ * osfm_ba_summary.order_arcs / chain_blocks*.  New entries and new structs (the view front end, its marks) leave it alone:
  * nothing that a caller built against 102 reads or writes has changed. */
 #define OSFM_ABI_VERSION 102
 OSFM_API int osfm_version(void);
@@ -1096,6 +1096,73 @@ OSFM_API int osfm_view_front_download(osfm_view_front *front, float *positions, 
 /* Test hook: the image the detectors saw; *width, *height, *channels (may be NULL) are always set, out (may be
  * NULL) takes width * height * channels bytes. */
 OSFM_API int osfm_view_front_debug_image(osfm_view_front *front, uint8_t *out, int32_t *width, int32_t *height, int32_t *channels);
+
+/* View masks and pixel colours: filterTracksWithMasks (src/matching/matching.cpp:325-368 with View::isPixelMaskedIn,
+ * src/data_structures/view.cpp:100-112) and propagateColorsToTracks (src/util/common.cpp:289-315) as per-row lookups
+ * at load time, while the import image is on the device.  Every row gets the pixel position the track conversion
+ * will give it (pixel_width * (normalised + 0.5) on BOTH axes, osfm_tracks_from_mve's expression), a mark byte and
+ * the colour of the import image's pixel under that position, truncated, not interpolated.
+ *   mark bit 0 (OSFM_MARK_IN)       the row is masked in: mask value > threshold, or the view has no mask
+ *   mark bit 1 (OSFM_MARK_OUTSIDE)  the reference's index lies outside the mask, where the reference reads past it;
+ *                                   such a row counts as masked out
+ * clamp OSFM_CLAMP_REFERENCE is the reference as written: x is clamped by rows - 1 and y by cols - 1, then the mask is
+ * read at row y, column x.  OSFM_CLAMP_IMAGE clamps x by cols - 1 and y by rows - 1 and never leaves the mask.
+ * The colour lookup clamps x by cols - 1 and y by rows - 1 of the import image, as the reference does.
+ * mode OSFM_MARK_TRACKS leaves the load's result exactly that of osfm_view_front_load, the marks ride beside it (for
+ * osfm_tracks_filter_marked).  OSFM_MARK_FEATURES removes the masked-out rows from the result: the summary's counts,
+ * both downloads and osfm_match_set_view_from_front see the kept rows only, in their order -- byte for byte what
+ * deleting those rows from a plain load's download gives.  That is not the reference (the ratio test sees fewer
+ * candidates); it is the cheaper form for a caller who matches the masked object only. */
+#define OSFM_MARK_TRACKS 0
+#define OSFM_MARK_FEATURES 1
+#define OSFM_CLAMP_REFERENCE 0
+#define OSFM_CLAMP_IMAGE 1
+#define OSFM_MARK_IN 1
+#define OSFM_MARK_OUTSIDE 2
+
+typedef struct osfm_view_mark_options {
+    int32_t mode;          /* OSFM_MARK_TRACKS */
+    int32_t clamp;         /* OSFM_CLAMP_REFERENCE */
+    int32_t threshold;     /* 16: a row is masked in where the mask value is above it */
+    int32_t pixel_width;   /* 0: this load's import_width -- the reference's imageWidth */
+} osfm_view_mark_options;
+OSFM_API int osfm_view_mark_options_default(osfm_view_mark_options *opts);
+
+typedef struct osfm_view_mark_summary {
+    int32_t masked_out_sift, masked_out_surf;   /* rows without OSFM_MARK_IN, per detector */
+    int32_t outside;                            /* of those, rows with OSFM_MARK_OUTSIDE */
+    int32_t kept_sift, kept_surf;               /* rows of the load's result (OSFM_MARK_TRACKS: every row) */
+    int32_t has_mask, pixel_width, reserved;
+} osfm_view_mark_summary;
+
+/* osfm_view_front_load with the marks.  mask [mask_height][mask_width] bytes in host memory, at whatever size the
+ * caller resized it to; NULL: a view without a mask (hasMask() false), which masks nothing.  opts NULL: the defaults.
+ * *summary and *mark_summary may be NULL.  A chain with two or more max_image_size halvings would overwrite the import
+ * image: the front end then takes a third image buffer (booked in osfm_library_memory), on the first such call.
+ * Errors as osfm_view_front_load, and OSFM_E_ARG for a mask size that is not positive or options out of range. */
+OSFM_API int osfm_view_front_load_marked(osfm_view_front *front, const uint8_t *pixels, int width, int height, int channels,
+    const uint8_t *mask, int mask_width, int mask_height, const osfm_view_mark_options *opts, osfm_view_summary *summary,
+    osfm_view_mark_summary *mark_summary);
+
+/* The marks of the last osfm_view_front_load_marked, in the order of osfm_view_front_download (the kept rows with
+ * OSFM_MARK_FEATURES); every output may be NULL: pixel_xy [n][2] float, pixel_rgb [n][3], mark [n].
+ * OSFM_E_STATE after a plain osfm_view_front_load, or without a load. */
+OSFM_API int osfm_view_front_download_marks(osfm_view_front *front, float *pixel_xy, uint8_t *pixel_rgb, uint8_t *mark);
+
+/* Test hook, host code, no device needed: the row function the marks kernel runs, on host arrays.  normalized [n][2];
+ * pixels is the import image; mask may be NULL; opts->mode is ignored and opts->pixel_width 0 means `width`. */
+OSFM_API int osfm_view_debug_mark_rows(int64_t n, const float *normalized, const uint8_t *pixels, int width, int height,
+    int channels, const uint8_t *mask, int mask_width, int mask_height, const osfm_view_mark_options *opts, float *pixel_xy,
+    uint8_t *pixel_rgb, uint8_t *mark);
+
+/* filterTracksWithMasks on tracks as CSR over (view, feature) -- osfm_tracks_compute's output -- and the marks of
+ * every view, concatenated: view v's rows start at view_starts[v].  Host code.  keep[t] = 1 where every feature of
+ * track t that lies in a view with a mask (view_has_mask[v] != 0) carries OSFM_MARK_IN; the marks of a view without
+ * a mask are not read, and with no mask on any view every track is kept, as the reference returns its input.
+ * *num_kept may be NULL.  OSFM_E_RANGE for a feature that names no row. */
+OSFM_API int osfm_tracks_filter_marked(int64_t num_tracks, const int64_t *track_offsets, const int32_t *track_features,
+    int32_t num_views, const int64_t *view_starts, const uint8_t *marks, const uint8_t *view_has_mask, uint8_t *keep,
+    int64_t *num_kept);
 
 /* Sets view `view` of the matcher from the front end's last load, on the device: what osfm_view_front_download ->
  * osfm_match_set_view_float -> osfm_match_set_positions (normalised, SIFT rows then SURF rows) would leave, byte for

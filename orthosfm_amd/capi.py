@@ -196,6 +196,22 @@ class ViewSummary(C.Structure):
                [(n, C.c_double) for n in ("halving_ms", "view_ms", "total_ms")]
 
 
+MARK_TRACKS, MARK_FEATURES = 0, 1
+CLAMP_REFERENCE, CLAMP_IMAGE = 0, 1
+MARK_IN, MARK_OUTSIDE = 1, 2
+
+
+class ViewMarkOptions(C.Structure):
+    """osfm_view_mark_options"""
+    _fields_ = [(n, C.c_int32) for n in ("mode", "clamp", "threshold", "pixel_width")]
+
+
+class ViewMarkSummary(C.Structure):
+    """osfm_view_mark_summary"""
+    _fields_ = [(n, C.c_int32) for n in ("masked_out_sift", "masked_out_surf", "outside", "kept_sift", "kept_surf", "has_mask",
+                                         "pixel_width", "reserved")]
+
+
 class ViewBank(C.Structure):
     """osfm_view_bank (test hook osfm_match_debug_view_bank)."""
     COUNTS = ("n_sift", "n_surf", "n_sift_pad", "n_surf_pad", "n_special", "n_special_pad", "surf_norm2_max", "n_positions")
@@ -248,6 +264,8 @@ EXPORTS = [
     "osfm_view_options_default", "osfm_view_front_create", "osfm_view_front_destroy", "osfm_view_front_load",
     "osfm_view_front_download", "osfm_view_front_debug_image", "osfm_match_set_view_from_front",
     "osfm_match_debug_view_bank", "osfm_match_debug_set_view_device",
+    "osfm_view_mark_options_default", "osfm_view_front_load_marked", "osfm_view_front_download_marks", "osfm_view_debug_mark_rows",
+    "osfm_tracks_filter_marked",
 ]
 
 # osfm_track_feature as a numpy record (32 bytes, no padding)
@@ -284,6 +302,13 @@ lib.osfm_view_front_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(View
 lib.osfm_view_front_destroy.argtypes = [C.c_void_p]
 lib.osfm_view_front_load.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewSummary)]
 lib.osfm_view_front_download.argtypes = [C.c_void_p] + [C.c_void_p] * 7
+lib.osfm_view_front_load_marked.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                            C.POINTER(ViewMarkOptions), C.POINTER(ViewSummary), C.POINTER(ViewMarkSummary)]
+lib.osfm_view_front_download_marks.argtypes = [C.c_void_p] + [C.c_void_p] * 3
+lib.osfm_view_debug_mark_rows.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                          C.POINTER(ViewMarkOptions), C.c_void_p, C.c_void_p, C.c_void_p]
+lib.osfm_tracks_filter_marked.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_int64)]
 lib.osfm_view_front_debug_image.argtypes = [C.c_void_p, C.c_void_p] + [C.POINTER(C.c_int32)] * 3
 lib.osfm_match_set_view_from_front.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
 lib.osfm_match_debug_view_bank.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(ViewBank)]
@@ -389,6 +414,12 @@ def default_surf_options() -> SurfOptions:
 def default_view_options() -> ViewOptions:
     o = ViewOptions()
     check(lib.osfm_view_options_default(C.byref(o)))
+    return o
+
+
+def default_view_mark_options() -> ViewMarkOptions:
+    o = ViewMarkOptions()
+    check(lib.osfm_view_mark_options_default(C.byref(o)))
     return o
 
 

@@ -496,4 +496,39 @@ int osfm_tracks_compute_ranges(int32_t num_views, const int32_t *view_sizes, con
         summary);
 }
 
+// filterTracksWithMasks (src/matching/matching.cpp:325-368): a track stays when none of its features in a view
+// with a mask is masked out; without a mask on any view the list comes back as it is.
+int osfm_tracks_filter_marked(int64_t num_tracks, const int64_t *track_offsets, const int32_t *track_features,
+    int32_t num_views, const int64_t *view_starts, const uint8_t *marks, const uint8_t *view_has_mask, uint8_t *keep,
+    int64_t *num_kept)
+{
+    if (num_tracks < 0 || num_views < 0 || !track_offsets || !view_starts || (num_views > 0 && !view_has_mask) ||
+        (num_tracks > 0 && !keep)) {
+        set_error("tracks_filter_marked: null argument / negative count");
+        return OSFM_E_ARG;
+    }
+    bool any = false;
+    for (int32_t v = 0; v < num_views; ++v) any |= view_has_mask[v] != 0;
+    if (num_tracks > 0 && track_offsets[num_tracks] > track_offsets[0] && (!track_features || (any && !marks))) {
+        set_error("tracks_filter_marked: null feature list / marks");
+        return OSFM_E_ARG;
+    }
+    int64_t kept = 0;
+    for (int64_t t = 0; t < num_tracks; ++t) {
+        uint8_t valid = 1;
+        for (int64_t k = track_offsets[t]; k < track_offsets[t + 1]; ++k) {
+            const int32_t v = track_features[2 * k], f = track_features[2 * k + 1];
+            if (v < 0 || v >= num_views || f < 0 || f >= view_starts[v + 1] - view_starts[v]) {
+                set_error("tracks_filter_marked: feature %lld names (%d, %d)", (long long)k, v, f);
+                return OSFM_E_RANGE;
+            }
+            if (any && valid && view_has_mask[v] && !(marks[view_starts[v] + f] & OSFM_MARK_IN)) valid = 0;
+        }
+        keep[t] = valid;
+        kept += valid;
+    }
+    if (num_kept) *num_kept = kept;
+    return OSFM_OK;
+}
+
 }  // extern "C"

@@ -4,6 +4,7 @@
 #include <memory>
 
 #include "feature_device.h"
+#include "feature_view.h"
 #include "osfm_common.h"
 #include "view_front.h"
 #include "view_kernels.h"
@@ -21,10 +22,16 @@ struct osfm_view_front {
     bool read_pending = false;
     size_t max_features = 0;
     DeviceBuffer img[2], positions, normalized, colors, sift_map, surf_map;
+    // osfm_view_front_load_marked: reserved by the first call that needs them.  img_keep: the third image buffer of
+    // a chain that would overwrite the import image; kept: the second set of arrays of OSFM_MARK_FEATURES
+    DeviceBuffer img_keep, mask, pixel_xy, pixel_rgb, mark, mark_counts, kept_index;
+    DeviceBuffer kept[8];                  // positions, normalized, colors, sift_map, surf_map, pixel_xy, pixel_rgb, mark
     // the last load
     bool have = false;
     int import_w = 0, import_h = 0, feat_w = 0, feat_h = 0, channels = 0, n_sift = 0, n_surf = 0;
     const uint8_t *d_image = nullptr;
+    bool have_marks = false, compacted = false;
+    bool host_rows_stale = false;          // compacted: the host arrays below still hold every row of the detectors
     DeviceFeatures fs, fu;
     std::vector<float> h_positions, h_scale, h_orientation;     // FeatureSet's order, SIFT rows first
     std::vector<int32_t> h_sift_map, h_surf_map;
@@ -61,7 +68,31 @@ bool plan_chain(const osfm_view_options &o, int w, int h, int *import_w, int *im
     return true;
 }
 
-int load(osfm_view_front *c, const uint8_t *pixels, int width, int height, int channels, osfm_view_summary *sum_out)
+// What osfm_view_front_load_marked adds to a load.
+struct MarkRequest {
+    const uint8_t *mask;
+    int mask_w, mask_h;
+    osfm_view_mark_options opts;
+    osfm_view_mark_summary *out;
+};
+
+view::ViewRows rows_of(osfm_view_front *c, bool kept)
+{
+    view::ViewRows r;
+    if (kept) {
+        r.positions = c->kept[0].as<float>(); r.normalized = c->kept[1].as<float>(); r.colors = c->kept[2].as<uint8_t>();
+        r.sift_map = c->kept[3].as<int32_t>(); r.surf_map = c->kept[4].as<int32_t>(); r.pixel_xy = c->kept[5].as<float>();
+        r.pixel_rgb = c->kept[6].as<uint8_t>(); r.mark = c->kept[7].as<uint8_t>();
+    } else {
+        r.positions = c->positions.as<float>(); r.normalized = c->normalized.as<float>(); r.colors = c->colors.as<uint8_t>();
+        r.sift_map = c->sift_map.as<int32_t>(); r.surf_map = c->surf_map.as<int32_t>(); r.pixel_xy = c->pixel_xy.as<float>();
+        r.pixel_rgb = c->pixel_rgb.as<uint8_t>(); r.mark = c->mark.as<uint8_t>();
+    }
+    return r;
+}
+
+int load(osfm_view_front *c, const uint8_t *pixels, int width, int height, int channels, osfm_view_summary *sum_out,
+    const MarkRequest *marks)
 {
     int iw, ih, fw, fh, halvings;
     if (!plan_chain(c->opts, width, height, &iw, &ih, &fw, &fh, &halvings)) {
@@ -70,6 +101,25 @@ int load(osfm_view_front *c, const uint8_t *pixels, int width, int height, int c
         return OSFM_E_ARG;
     }
     hipStream_t s = c->stream;
+    // the marks read the import image after the detectors have run: where the chain goes on for two or more
+    // halvings behind it, these alternate between the other buffer and a third one
+    const int import_at = c->opts.downscale_factor - 1;
+    const bool keep_import = marks && halvings - import_at >= 2;
+    if (marks) {
+        const size_t K = c->max_features;
+        const bool features = marks->opts.mode == OSFM_MARK_FEATURES;
+        if (keep_import) OSFM_RETURN_IF(c->img_keep.reserve((size_t)((iw + 3) >> 2) * ((ih + 3) >> 2) * channels));
+        if (marks->mask) OSFM_RETURN_IF(c->mask.reserve((size_t)marks->mask_w * marks->mask_h));
+        OSFM_RETURN_IF(c->pixel_xy.reserve(K * 8));
+        OSFM_RETURN_IF(c->pixel_rgb.reserve(K * 3));
+        OSFM_RETURN_IF(c->mark.reserve(K));
+        OSFM_RETURN_IF(c->mark_counts.reserve(32));
+        if (features && marks->mask) {
+            const size_t row_bytes[8] = {8, 8, 3, 4, 4, 8, 3, 1};
+            for (int k = 0; k < 8; ++k) OSFM_RETURN_IF(c->kept[k].reserve(K * row_bytes[k]));
+            OSFM_RETURN_IF(c->kept_index.reserve(K * 4));
+        }
+    }
     // a hand-off that still reads the previous load's arrays: this load's work queues behind it, the host does not wait
     if (c->read_pending) {
         OSFM_HIP_CHECK(hipStreamWaitEvent(s, c->read_done, 0));
@@ -77,15 +127,24 @@ int load(osfm_view_front *c, const uint8_t *pixels, int width, int height, int c
     }
     OSFM_HIP_CHECK(hipMemcpyAsync(c->img[0].ptr, pixels, (size_t)width * height * channels, hipMemcpyHostToDevice, s));
     OSFM_HIP_CHECK(hipEventRecord(c->ev[0], s));
+    if (marks && marks->mask)
+        OSFM_HIP_CHECK(hipMemcpyAsync(c->mask.ptr, marks->mask, (size_t)marks->mask_w * marks->mask_h, hipMemcpyHostToDevice, s));
+    uint8_t *bufs[3] = {c->img[0].as<uint8_t>(), c->img[1].as<uint8_t>(), c->img_keep.as<uint8_t>()};
     int cur = 0, w = width, h = height;
+    const uint8_t *d_import = bufs[0];
     for (int i = 0; i < halvings; ++i) {
-        view::launch_halve(s, c->img[cur].as<uint8_t>(), w, h, channels, c->img[cur ^ 1].as<uint8_t>());
+        // without keep_import: the two buffers in turn.  With it, from the second halving behind the import image
+        // on, the buffer that is neither the import image's nor the current one
+        int to = cur ^ 1;
+        if (keep_import && i > import_at) to = 3 - (import_at & 1) - cur;
+        view::launch_halve(s, bufs[cur], w, h, channels, bufs[to]);
         half(&w, &h);
-        cur ^= 1;
+        cur = to;
+        if (i + 1 == import_at) d_import = bufs[cur];
     }
     OSFM_HIP_CHECK(hipGetLastError());
     OSFM_HIP_CHECK(hipEventRecord(c->ev[1], s));
-    const uint8_t *d_image = c->img[cur].as<uint8_t>();
+    const uint8_t *d_image = bufs[cur];
 
     osfm_view_summary sum;
     std::memset(&sum, 0, sizeof(sum));
@@ -123,6 +182,23 @@ int load(osfm_view_front *c, const uint8_t *pixels, int width, int height, int c
     view::launch_view_rows(s, d_image, fw, fh, channels, c->positions.as<float>(), n, c->colors.as<uint8_t>(),
         c->normalized.as<float>());
     OSFM_HIP_CHECK(hipGetLastError());
+    int32_t h_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // [0..2]: the marks kernel's, [4..5]: the compaction's
+    bool compacted = false;
+    int pixel_width = 0;
+    if (marks) {
+        const osfm_view_mark_options &mo = marks->opts;
+        pixel_width = mo.pixel_width > 0 ? mo.pixel_width : iw;
+        int32_t *counts = c->mark_counts.as<int32_t>();
+        OSFM_HIP_CHECK(hipMemsetAsync(counts, 0, 32, s));
+        view::launch_view_marks(s, c->normalized.as<float>(), n, ns, (double)pixel_width, d_import, iw, ih, channels,
+            marks->mask ? c->mask.as<uint8_t>() : nullptr, marks->mask_w, marks->mask_h, mo.clamp, mo.threshold,
+            c->pixel_xy.as<float>(), c->pixel_rgb.as<uint8_t>(), c->mark.as<uint8_t>(), counts);
+        // a view without a mask keeps every row: nothing to move
+        compacted = mo.mode == OSFM_MARK_FEATURES && marks->mask && n > 0;
+        if (compacted) view::launch_compact_rows(s, rows_of(c, false), ns, nu, rows_of(c, true), c->kept_index.as<int32_t>(), counts + 4);
+        OSFM_HIP_CHECK(hipGetLastError());
+        OSFM_HIP_CHECK(hipMemcpyAsync(h_counts, counts, 32, hipMemcpyDeviceToHost, s));
+    }
     OSFM_HIP_CHECK(hipEventRecord(c->ev[3], s));
     OSFM_HIP_CHECK(hipStreamSynchronize(s));
 
@@ -135,6 +211,22 @@ int load(osfm_view_front *c, const uint8_t *pixels, int width, int height, int c
     sum.total_ms = (double)chain_ms + view_ms + sum.sift.total_ms + sum.surf.total_ms;
     c->import_w = iw; c->import_h = ih; c->feat_w = fw; c->feat_h = fh; c->channels = channels;
     c->n_sift = ns; c->n_surf = nu; c->d_image = d_image;
+    c->have_marks = marks != nullptr; c->compacted = compacted; c->host_rows_stale = compacted;
+    if (marks) {
+        osfm_view_mark_summary ms;
+        std::memset(&ms, 0, sizeof(ms));
+        ms.masked_out_sift = h_counts[0]; ms.masked_out_surf = h_counts[1]; ms.outside = h_counts[2];
+        ms.kept_sift = compacted ? h_counts[4] : ns; ms.kept_surf = compacted ? h_counts[5] : nu;
+        ms.has_mask = marks->mask != nullptr; ms.pixel_width = pixel_width;
+        if (compacted && (ms.kept_sift != ns - ms.masked_out_sift || ms.kept_surf != nu - ms.masked_out_surf)) {
+            set_error("osfm_view_front_load_marked: internal: %d + %d rows kept, %d + %d of %d + %d masked out", ms.kept_sift,
+                ms.kept_surf, ms.masked_out_sift, ms.masked_out_surf, ns, nu);
+            return OSFM_E_STATE;
+        }
+        c->n_sift = ms.kept_sift; c->n_surf = ms.kept_surf;
+        sum.num_sift = ms.kept_sift; sum.num_surf = ms.kept_surf;
+        if (marks->out) *marks->out = ms;
+    }
     c->have = true;
     if (sum_out) *sum_out = sum;
     return OSFM_OK;
@@ -152,6 +244,45 @@ int download_rows(osfm_view_front *c, const float *desc, const std::vector<int32
     return OSFM_OK;
 }
 
+// After a load that moved the kept rows together on the device, the host's arrays follow on the first download: the
+// load itself waits for the two counts alone.
+int refresh_host_rows(osfm_view_front *c)
+{
+    if (!c->host_rows_stale) return OSFM_OK;
+    const size_t ns = (size_t)c->n_sift, nu = (size_t)c->n_surf, n = ns + nu;
+    std::vector<int32_t> index(n), sift_map(ns), surf_map(nu);
+    if (n) OSFM_HIP_CHECK(hipMemcpyAsync(index.data(), c->kept_index.ptr, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (ns) OSFM_HIP_CHECK(hipMemcpyAsync(sift_map.data(), c->kept[3].ptr, ns * 4, hipMemcpyDeviceToHost, c->stream));
+    if (nu) OSFM_HIP_CHECK(hipMemcpyAsync(surf_map.data(), c->kept[4].ptr, nu * 4, hipMemcpyDeviceToHost, c->stream));
+    OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n; ++i) {            // index ascends and index[i] >= i: in place
+        const size_t r = (size_t)index[i];
+        c->h_positions[2 * i] = c->h_positions[2 * r]; c->h_positions[2 * i + 1] = c->h_positions[2 * r + 1];
+        c->h_scale[i] = c->h_scale[r]; c->h_orientation[i] = c->h_orientation[r];
+    }
+    c->h_positions.resize(n * 2); c->h_scale.resize(n); c->h_orientation.resize(n);
+    c->h_sift_map.swap(sift_map); c->h_surf_map.swap(surf_map);
+    c->host_rows_stale = false;
+    return OSFM_OK;
+}
+
+int check_load_args(osfm_view_front *c, const uint8_t *pixels, int width, int height, int channels, const char *who)
+{
+    if (!c || !pixels) { set_error("%s: null argument", who); return OSFM_E_ARG; }
+    c->have = false;          // whatever comes of this call, the previous result is gone
+    c->have_marks = false;
+    if (channels != 1 && channels != 3) {
+        set_error("%s: %d channels: a grey (1) or colour (3) image is expected", who, channels);
+        return OSFM_E_ARG;
+    }
+    if (width < 1 || height < 1) { set_error("%s: image size %d x %d", who, width, height); return OSFM_E_ARG; }
+    if (width > c->max_w || height > c->max_h) {
+        set_error("%s: a %d x %d image exceeds the front end's %d x %d", who, width, height, c->max_w, c->max_h);
+        return OSFM_E_RANGE;
+    }
+    return OSFM_OK;
+}
+
 }  // namespace
 
 namespace osfm {
@@ -161,8 +292,9 @@ int view_front_result(osfm_view_front *c, FrontResult *out)
     if (!c || !out) { set_error("osfm_view_front: null argument"); return OSFM_E_ARG; }
     if (!c->have) { set_error("osfm_view_front: no load to hand off"); return OSFM_E_STATE; }
     out->device = c->device;
-    out->sift_desc = c->fs.desc; out->surf_desc = c->fu.desc; out->normalized = c->normalized.as<float>();
-    out->sift_map = c->sift_map.as<int32_t>(); out->surf_map = c->surf_map.as<int32_t>();
+    const view::ViewRows rows = rows_of(c, c->compacted);
+    out->sift_desc = c->fs.desc; out->surf_desc = c->fu.desc; out->normalized = rows.normalized;
+    out->sift_map = rows.sift_map; out->surf_map = rows.surf_map;
     out->n_sift = c->n_sift; out->n_surf = c->n_surf;
     return OSFM_OK;
 }
@@ -261,21 +393,87 @@ int osfm_view_front_destroy(osfm_view_front *c)
 
 int osfm_view_front_load(osfm_view_front *c, const uint8_t *pixels, int width, int height, int channels, osfm_view_summary *summary)
 {
-    if (!c || !pixels) { set_error("osfm_view_front_load: null argument"); return OSFM_E_ARG; }
-    c->have = false;          // whatever comes of this call, the previous result is gone
-    if (channels != 1 && channels != 3) {
-        set_error("osfm_view_front_load: %d channels: a grey (1) or colour (3) image is expected", channels);
-        return OSFM_E_ARG;
-    }
-    if (width < 1 || height < 1) { set_error("osfm_view_front_load: image size %d x %d", width, height); return OSFM_E_ARG; }
-    if (width > c->max_w || height > c->max_h) {
-        set_error("osfm_view_front_load: a %d x %d image exceeds the front end's %d x %d", width, height, c->max_w, c->max_h);
-        return OSFM_E_RANGE;
-    }
+    OSFM_RETURN_IF(check_load_args(c, pixels, width, height, channels, "osfm_view_front_load"));
     OSFM_HIP_CHECK(hipSetDevice(c->device));
-    const int rc = load(c, pixels, width, height, channels, summary);
+    const int rc = load(c, pixels, width, height, channels, summary, nullptr);
     if (rc != OSFM_OK) (void)hipStreamSynchronize(c->stream);   // nothing of a failed call may still run
     return rc;
+}
+
+int osfm_view_mark_options_default(osfm_view_mark_options *o)
+{
+    if (!o) { set_error("osfm_view_mark_options_default: null argument"); return OSFM_E_ARG; }
+    o->mode = OSFM_MARK_TRACKS;
+    o->clamp = OSFM_CLAMP_REFERENCE;
+    o->threshold = 16;
+    o->pixel_width = 0;
+    return OSFM_OK;
+}
+
+static int check_mark_args(const uint8_t *mask, int mask_w, int mask_h, const osfm_view_mark_options &o, const char *who)
+{
+    if (mask && (mask_w < 1 || mask_h < 1)) { set_error("%s: mask size %d x %d", who, mask_w, mask_h); return OSFM_E_ARG; }
+    if ((o.mode != OSFM_MARK_TRACKS && o.mode != OSFM_MARK_FEATURES) || (o.clamp != OSFM_CLAMP_REFERENCE && o.clamp != OSFM_CLAMP_IMAGE) ||
+        o.pixel_width < 0) {
+        set_error("%s: invalid options (mode 0..1, clamp 0..1, pixel_width >= 0)", who);
+        return OSFM_E_ARG;
+    }
+    return OSFM_OK;
+}
+
+int osfm_view_front_load_marked(osfm_view_front *c, const uint8_t *pixels, int width, int height, int channels, const uint8_t *mask,
+    int mask_width, int mask_height, const osfm_view_mark_options *opts, osfm_view_summary *summary, osfm_view_mark_summary *mark_summary)
+{
+    OSFM_RETURN_IF(check_load_args(c, pixels, width, height, channels, "osfm_view_front_load_marked"));
+    MarkRequest req;
+    (void)osfm_view_mark_options_default(&req.opts);
+    if (opts) req.opts = *opts;
+    req.mask = mask; req.mask_w = mask ? mask_width : 0; req.mask_h = mask ? mask_height : 0; req.out = mark_summary;
+    OSFM_RETURN_IF(check_mark_args(mask, mask_width, mask_height, req.opts, "osfm_view_front_load_marked"));
+    OSFM_HIP_CHECK(hipSetDevice(c->device));
+    const int rc = load(c, pixels, width, height, channels, summary, &req);
+    if (rc != OSFM_OK) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int osfm_view_front_download_marks(osfm_view_front *c, float *pixel_xy, uint8_t *pixel_rgb, uint8_t *mark)
+{
+    if (!c) { set_error("osfm_view_front_download_marks: null argument"); return OSFM_E_ARG; }
+    if (!c->have || !c->have_marks) {
+        set_error("osfm_view_front_download_marks: no osfm_view_front_load_marked to download");
+        return OSFM_E_STATE;
+    }
+    OSFM_HIP_CHECK(hipSetDevice(c->device));
+    const size_t n = (size_t)c->n_sift + c->n_surf;
+    const view::ViewRows rows = rows_of(c, c->compacted);
+    if (pixel_xy && n) OSFM_HIP_CHECK(hipMemcpyAsync(pixel_xy, rows.pixel_xy, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (pixel_rgb && n) OSFM_HIP_CHECK(hipMemcpyAsync(pixel_rgb, rows.pixel_rgb, n * 3, hipMemcpyDeviceToHost, c->stream));
+    if (mark && n) OSFM_HIP_CHECK(hipMemcpyAsync(mark, rows.mark, n, hipMemcpyDeviceToHost, c->stream));
+    OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return OSFM_OK;
+}
+
+int osfm_view_debug_mark_rows(int64_t n, const float *normalized, const uint8_t *pixels, int width, int height, int channels,
+    const uint8_t *mask, int mask_width, int mask_height, const osfm_view_mark_options *opts, float *pixel_xy, uint8_t *pixel_rgb,
+    uint8_t *mark)
+{
+    if (n < 0 || !pixels || (n > 0 && (!normalized || !pixel_xy || !pixel_rgb || !mark))) {
+        set_error("osfm_view_debug_mark_rows: null argument / negative count");
+        return OSFM_E_ARG;
+    }
+    if ((channels != 1 && channels != 3) || width < 1 || height < 1) {
+        set_error("osfm_view_debug_mark_rows: a %d x %d image of %d channels", width, height, channels);
+        return OSFM_E_ARG;
+    }
+    osfm_view_mark_options o;
+    (void)osfm_view_mark_options_default(&o);
+    if (opts) o = *opts;
+    OSFM_RETURN_IF(check_mark_args(mask, mask_width, mask_height, o, "osfm_view_debug_mark_rows"));
+    const double pixel_width = o.pixel_width > 0 ? o.pixel_width : width;
+    for (int64_t i = 0; i < n; ++i)
+        view_mark_row(normalized[2 * i], normalized[2 * i + 1], pixel_width, pixels, width, height, channels, mask, mask_width,
+            mask_height, o.clamp, o.threshold, pixel_xy + 2 * i, mark + i, pixel_rgb + 3 * i);
+    return OSFM_OK;
 }
 
 int osfm_view_front_download(osfm_view_front *c, float *positions, float *normalized, uint8_t *colors, float *scale,
@@ -284,12 +482,14 @@ int osfm_view_front_download(osfm_view_front *c, float *positions, float *normal
     if (!c) { set_error("osfm_view_front_download: null argument"); return OSFM_E_ARG; }
     if (!c->have) { set_error("osfm_view_front_download: no load to download"); return OSFM_E_STATE; }
     OSFM_HIP_CHECK(hipSetDevice(c->device));
+    OSFM_RETURN_IF(refresh_host_rows(c));
     const size_t n = (size_t)c->n_sift + c->n_surf;
+    const view::ViewRows rows = rows_of(c, c->compacted);
     if (positions && n) std::memcpy(positions, c->h_positions.data(), n * 8);
     if (scale && n) std::memcpy(scale, c->h_scale.data(), n * 4);
     if (orientation && n) std::memcpy(orientation, c->h_orientation.data(), n * 4);
-    if (normalized && n) OSFM_HIP_CHECK(hipMemcpyAsync(normalized, c->normalized.ptr, n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (colors && n) OSFM_HIP_CHECK(hipMemcpyAsync(colors, c->colors.ptr, n * 3, hipMemcpyDeviceToHost, c->stream));
+    if (normalized && n) OSFM_HIP_CHECK(hipMemcpyAsync(normalized, rows.normalized, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (colors && n) OSFM_HIP_CHECK(hipMemcpyAsync(colors, rows.colors, n * 3, hipMemcpyDeviceToHost, c->stream));
     OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
     if (sift_descriptors) OSFM_RETURN_IF(download_rows(c, c->fs.desc, c->h_sift_map, 128, sift_descriptors));
     if (surf_descriptors) OSFM_RETURN_IF(download_rows(c, c->fu.desc, c->h_surf_map, 64, surf_descriptors));

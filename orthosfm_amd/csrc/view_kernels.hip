@@ -3,6 +3,8 @@
 // host's (feature_view.h, osfm_quantize_sift / osfm_quantize_surf) operation for operation.
 #include "view_kernels.h"
 
+#include "feature_view.h"
+
 namespace osfm {
 namespace view {
 
@@ -81,6 +83,92 @@ view_rows_kernel(const uint8_t *__restrict__ img, int w, int h, int ch, const fl
     nrm.x = (px + 0.5f - fw * 0.5f) / fnorm;
     nrm.y = (py + 0.5f - fh * 0.5f) / fnorm;
     reinterpret_cast<float2 *>(normalized)[i] = nrm;
+}
+
+// view_mark_row of feature_view.h, one lane per row: three byte gathers (mask, pixel) and 12 bytes written.  A wave
+// adds what it counted in one atomic per counter, and only where it counted something.
+__global__ void __launch_bounds__(kThreads)
+view_marks_kernel(const float *__restrict__ normalized, int n, int n_sift, double pixel_width, const uint8_t *__restrict__ img,
+    int w, int h, int ch, const uint8_t *__restrict__ mask, int mask_w, int mask_h, int clamp, int threshold,
+    float *__restrict__ pixel_xy, uint8_t *__restrict__ pixel_rgb, uint8_t *__restrict__ mark, int32_t *__restrict__ counts)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    uint8_t m = kMarkIn;
+    if (i < n) {
+        const float2 p = reinterpret_cast<const float2 *>(normalized)[i];
+        float xy[2];
+        uint8_t rgb[3];
+        view_mark_row(p.x, p.y, pixel_width, img, w, h, ch, mask, mask_w, mask_h, clamp, threshold, xy, &m, rgb);
+        float2 o;
+        o.x = xy[0]; o.y = xy[1];
+        reinterpret_cast<float2 *>(pixel_xy)[i] = o;
+        for (int k = 0; k < 3; ++k) pixel_rgb[3 * (size_t)i + k] = rgb[k];
+        mark[i] = m;
+    }
+    const bool out = !(m & kMarkIn);        // lanes past n carry kMarkIn and count nowhere
+    const int c0 = __popcll(__ballot(out && i < n_sift)), c1 = __popcll(__ballot(out && i >= n_sift));
+    const int c2 = __popcll(__ballot((m & kMarkOutside) != 0));
+    if ((threadIdx.x & 63) == 0) {
+        if (c0) atomicAdd(counts + 0, c0);
+        if (c1) atomicAdd(counts + 1, c1);
+        if (c2) atomicAdd(counts + 2, c2);
+    }
+}
+
+// One workgroup.  A pass takes kCompactPassRows rows, a thread four neighbours of them; the kept rows of a pass are
+// numbered by a scan over the threads (inside a wave by shuffles, across the four waves through LDS) on top of
+// what the earlier passes kept, which every thread adds up for itself.  The SIFT rows come first and their passes
+// end at n_sift, so that the SURF rows are numbered from the kept SIFT rows on.
+constexpr int kCompactPerThread = kCompactPassRows / kThreads;
+
+__global__ void __launch_bounds__(kThreads)
+compact_rows_kernel(ViewRows from, int n_sift, int n_surf, ViewRows to, int32_t *__restrict__ index, int32_t *__restrict__ counts)
+{
+    __shared__ int32_t wave_sum[kThreads / 64];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    int kept = 0, kept_sift = 0;
+    for (int part = 0; part < 2; ++part) {
+        const int lo = part ? n_sift : 0, hi = part ? n_sift + n_surf : n_sift;
+        for (int pass = lo; pass < hi; pass += kCompactPassRows) {
+            const int r0 = pass + t * kCompactPerThread;
+            bool keep[kCompactPerThread];
+            int mine = 0;
+#pragma unroll
+            for (int k = 0; k < kCompactPerThread; ++k) {
+                keep[k] = r0 + k < hi && (from.mark[r0 + k] & kMarkIn);
+                mine += keep[k];
+            }
+            int incl = mine;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int up = __shfl_up(incl, d);
+                if (lane >= d) incl += up;
+            }
+            if (lane == 63) wave_sum[wave] = incl;
+            __syncthreads();
+            int before = 0, total = 0;
+#pragma unroll
+            for (int v = 0; v < kThreads / 64; ++v) { before += v < wave ? wave_sum[v] : 0; total += wave_sum[v]; }
+            int dst = kept + before + incl - mine;
+#pragma unroll
+            for (int k = 0; k < kCompactPerThread; ++k) {
+                if (!keep[k]) continue;
+                const size_t r = (size_t)(r0 + k), d = (size_t)dst++;
+                if (part == 0) to.sift_map[d] = from.sift_map[r];
+                else to.surf_map[d - kept_sift] = from.surf_map[r - n_sift];
+                reinterpret_cast<float2 *>(to.positions)[d] = reinterpret_cast<const float2 *>(from.positions)[r];
+                reinterpret_cast<float2 *>(to.normalized)[d] = reinterpret_cast<const float2 *>(from.normalized)[r];
+                reinterpret_cast<float2 *>(to.pixel_xy)[d] = reinterpret_cast<const float2 *>(from.pixel_xy)[r];
+                for (int q = 0; q < 3; ++q) { to.colors[3 * d + q] = from.colors[3 * r + q]; to.pixel_rgb[3 * d + q] = from.pixel_rgb[3 * r + q]; }
+                to.mark[d] = from.mark[r];
+                index[d] = (int32_t)r;
+            }
+            kept += total;
+            __syncthreads();            // wave_sum is written again in the next pass
+        }
+        if (part == 0) kept_sift = kept;
+    }
+    if (t == 0) { counts[0] = kept_sift; counts[1] = kept - kept_sift; }
 }
 
 // osfm_quantize_sift / osfm_quantize_surf (match_api.hip) for one value
@@ -212,6 +300,21 @@ void launch_view_rows(hipStream_t s, const uint8_t *img, int w, int h, int c, co
     if (n <= 0) return;
     hipLaunchKernelGGL(view_rows_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, img, w, h, c, positions, n,
         colors, normalized);
+}
+
+void launch_view_marks(hipStream_t s, const float *normalized, int n, int n_sift, double pixel_width, const uint8_t *img, int w,
+    int h, int c, const uint8_t *mask, int mask_w, int mask_h, int clamp, int threshold, float *pixel_xy, uint8_t *pixel_rgb,
+    uint8_t *mark, int32_t *counts)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(view_marks_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, normalized, n, n_sift,
+        pixel_width, img, w, h, c, mask, mask_w, mask_h, clamp, threshold, pixel_xy, pixel_rgb, mark, counts);
+}
+
+void launch_compact_rows(hipStream_t s, const ViewRows &from, int n_sift, int n_surf, const ViewRows &to, int32_t *index,
+    int32_t *counts)
+{
+    hipLaunchKernelGGL(compact_rows_kernel, dim3(1), dim3(kThreads), 0, s, from, n_sift, n_surf, to, index, counts);
 }
 
 void launch_handoff_sift(hipStream_t s, const float *desc, const int32_t *map, int n, int npad, int8_t *dst, int32_t *corr,

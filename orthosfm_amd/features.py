@@ -250,6 +250,36 @@ class ViewFeatures(FeatureSet):
     feature_height: int = 0
 
 
+_MARK_MODES = {"tracks": capi.MARK_TRACKS, "features": capi.MARK_FEATURES}
+_MARK_CLAMPS = {"reference": capi.CLAMP_REFERENCE, "image": capi.CLAMP_IMAGE}
+
+
+def _mark_options(mode, clamp, threshold, pixel_width):
+    if mode not in _MARK_MODES:
+        raise ValueError(f"mask mode {mode!r}: 'tracks' or 'features'")
+    if clamp not in _MARK_CLAMPS:
+        raise ValueError(f"mask clamp {clamp!r}: 'reference' or 'image'")
+    return capi.ViewMarkOptions(_MARK_MODES[mode], _MARK_CLAMPS[clamp], int(threshold), int(pixel_width))
+
+
+def mark_rows_host(normalized, image, mask=None, clamp="reference", threshold=16, pixel_width=0):
+    """Test hook osfm_view_debug_mark_rows: the row function of the marks kernel on host arrays, no device needed.
+    Returns (pixel_xy, pixel_rgb, mark) for normalized [n, 2]; image is the import image."""
+    image, channels = _image_arg("mark_rows_host", image)
+    nrm = np.ascontiguousarray(normalized, dtype=np.float32).reshape(-1, 2)
+    o = _mark_options("tracks", clamp, threshold, pixel_width)
+    mw = mh = 0
+    if mask is not None:
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        mh, mw = mask.shape
+    n = nrm.shape[0]
+    xy, rgb, mark = np.zeros((n, 2), np.float32), np.zeros((n, 3), np.uint8), np.zeros(n, np.uint8)
+    capi.check(capi.lib.osfm_view_debug_mark_rows(n, nrm.ctypes.data, image.ctypes.data, image.shape[1], image.shape[0], channels,
+                                                  mask.ctypes.data if mask is not None else None, mw, mh, C.byref(o),
+                                                  xy.ctypes.data, rgb.ctypes.data, mark.ctypes.data))
+    return xy, rgb, mark
+
+
 class ViewFrontEnd:
     """One context (osfm_view_front) for images up to max_width x max_height: image in host memory -> halving
     chain -> SIFT and SURF from one upload -> colours and normalised positions, all on the device.  `sift` and
@@ -264,7 +294,7 @@ class ViewFrontEnd:
                 if not hasattr(o, k):
                     raise TypeError(f"ViewFrontEnd: unknown {who} option {k!r}")
                 setattr(o, k, v)
-        self.options, self.summary = vo, None
+        self.options, self.summary, self.mark_summary = vo, None, None
         self._h = C.c_void_p()
         capi.check(capi.lib.osfm_view_front_create(device, int(max_width), int(max_height), C.byref(vo), C.byref(so), C.byref(uo),
                                                    C.byref(self._h)))
@@ -290,11 +320,44 @@ class ViewFrontEnd:
         """osfm_view_front_load: the summary (sizes, counts, stage times); the result stays on the device for
         HipExhaustiveMatching.set_view_from_front and download()."""
         image, channels = _image_arg("ViewFrontEnd", image)
-        self.summary = None
+        self.summary = self.mark_summary = None
         s = capi.ViewSummary()
         capi.check(capi.lib.osfm_view_front_load(self._h, image.ctypes.data, image.shape[1], image.shape[0], channels, C.byref(s)))
         self.summary = s
         return s
+
+    def load_marked(self, image, mask=None, mode="tracks", clamp="reference", threshold=16, pixel_width=0) -> capi.ViewSummary:
+        """osfm_view_front_load_marked: load() with a mark, a pixel position and a pixel colour per row
+        (filterTracksWithMasks and propagateColorsToTracks as lookups while the image is on the device).  mask: uint8
+        [mh, mw] at whatever size the caller resized it to, or None for a view without one.  mode "tracks" leaves the
+        result that of load(); "features" removes the masked-out rows from it.  clamp "reference" is the reference's
+        swapped clamp, "image" the intended one.  mark_summary holds the counts; download_marks() the arrays."""
+        image, channels = _image_arg("ViewFrontEnd", image)
+        o = _mark_options(mode, clamp, threshold, pixel_width)
+        mw = mh = 0
+        if mask is not None:
+            mask = np.asarray(mask)
+            if mask.dtype != np.uint8 or mask.ndim != 2:
+                raise TypeError("ViewFrontEnd: an uint8 mask [h, w] is expected")
+            mask = np.ascontiguousarray(mask)
+            mh, mw = mask.shape
+        self.summary = self.mark_summary = None
+        s, ms = capi.ViewSummary(), capi.ViewMarkSummary()
+        capi.check(capi.lib.osfm_view_front_load_marked(self._h, image.ctypes.data, image.shape[1], image.shape[0], channels,
+                                                        mask.ctypes.data if mask is not None else None, mw, mh, C.byref(o),
+                                                        C.byref(s), C.byref(ms)))
+        self.summary, self.mark_summary = s, ms
+        return s
+
+    def download_marks(self):
+        """osfm_view_front_download_marks of the last load_marked(): (pixel_xy float32 [n, 2], pixel_rgb uint8 [n, 3],
+        mark uint8 [n]) in download()'s row order."""
+        if self.summary is None:
+            raise capi.OsfmError(capi.E_STATE, "ViewFrontEnd.download_marks: no load to download")
+        n = self.summary.num_sift + self.summary.num_surf
+        xy, rgb, mark = np.zeros((n, 2), np.float32), np.zeros((n, 3), np.uint8), np.zeros(n, np.uint8)
+        capi.check(capi.lib.osfm_view_front_download_marks(self._h, xy.ctypes.data, rgb.ctypes.data, mark.ctypes.data))
+        return xy, rgb, mark
 
     def download(self) -> ViewFeatures:
         """osfm_view_front_download of the last load()."""

@@ -443,35 +443,84 @@ def match_and_build_tracks(iset, matcher="exhaustive", device=0, verify=True, ti
 
 
 def tracks_from_images(images, matcher="exhaustive", device=0, verify=True, downscale_factor=1, max_image_size=6_000_000,
-                       options=None, timings=None, pairs=None):
+                       options=None, timings=None, pairs=None, masks=None, mask_mode="tracks", mask_clamp="reference",
+                       feature_colors=False):
     """calculateTracksUsingMVE from decoded images onwards: every image (uint8 [h, w] or [h, w, 3]) goes through a
     features.ViewFrontEnd -- the halving chain, SIFT and SURF, colours and normalised positions on the device -- and
     from there into the matcher without the descriptors' way through the host; then matching, RANSAC-F, the tracks
     and the reference's pixel conversion, import_width * (pos + 0.5) on BOTH axes with pos normalised by the size of
     the feature image (matching_mve.cpp:455-466; import_width is the last view's, as the reference's imageWidth is
     whichever view wrote it last).  options: the capi.MatchOptions to start from (geometric_verification and the
-    matcher type are set here).  Returns (TrackTable, track colours (num_tracks, 3) uint8, info)."""
-    from .features import ViewFrontEnd
+    matcher type are set here).  Returns (TrackTable, track colours (num_tracks, 3) uint8, info).
+
+    masks: one uint8 mask [mh, mw] or None per image, the reference's --mask-folder (reconstruct.cpp:47-53).  With
+    mask_mode "tracks" the tracks go through filterTracksWithMasks: a track with a feature where its view's mask is
+    <= 16 is removed from the table and the colours.  With "features" such rows never enter the matcher, which is
+    cheaper and not the reference (the ratio test sees fewer candidates).  mask_clamp: "reference" (the swapped clamp
+    of View::isPixelMaskedIn as written) or "image".  feature_colors: info["feature_rgb"] holds
+    propagateColorsToTracks' colour per track feature, in the table's feature order, for save_project.  Either needs
+    one import width for all views, else ValueError: the reference's imageWidth there is whichever thread wrote last.
+    info["mask"] carries the counts."""
+    from .features import ViewFrontEnd, _mark_options
     images = [np.asarray(im) for im in images]
     if not images:
         raise ValueError("tracks_from_images: no images")
+    V = len(images)
+    marked = masks is not None or feature_colors
+    if marked:
+        _mark_options(mask_mode, mask_clamp, 16, 0)
+        if masks is not None and len(masks) != V:
+            raise ValueError("tracks_from_images: one mask (or None) per image")
+        widths = set()
+        for im in images:
+            w = int(im.shape[1])
+            for _ in range(1, downscale_factor):
+                w = (w + 1) >> 1
+            widths.add(w)
+        if len(widths) > 1:
+            raise ValueError(f"tracks_from_images: masks and feature colours need one import width, the views have {sorted(widths)}")
     front = ViewFrontEnd(device, max(im.shape[1] for im in images), max(im.shape[0] for im in images), downscale_factor,
                          max_image_size)
-    colors, width = [None] * len(images), [0]
+    colors, width = [None] * V, [0]
+    norms, marks, pixel_rgb, counts = [None] * V, [None] * V, [None] * V, [None] * V
 
     def upload(m, v):
-        s = front.load(images[v])
+        if marked:
+            s = front.load_marked(images[v], None if masks is None else masks[v], mask_mode, mask_clamp)
+        else:
+            s = front.load(images[v])
         m.set_view_from_front(v, front)
         fs = front.download()
         colors[v], width[0] = fs.colors, s.import_width
+        if marked:
+            _, pixel_rgb[v], marks[v] = front.download_marks()
+            norms[v], counts[v] = fs.normalized, front.mark_summary
         return fs.normalized
 
     try:
-        tt, info, tcol = _match_and_build(len(images), upload, None, lambda: width[0], matcher, device, verify, timings, pairs,
+        tt, info, tcol = _match_and_build(V, upload, None, lambda: width[0], matcher, device, verify, timings, pairs,
                                           options, colors)
-        return tt, tcol, info
     finally:
         front.close()
+    if not marked:
+        return tt, tcol, info
+    has_mask = [masks is not None and masks[v] is not None for v in range(V)]
+    mask_info = {"mode": mask_mode, "clamp": mask_clamp, "tracks_built": int(tt.offsets.shape[0] - 1), "tracks_dropped": 0}
+    for k in ("masked_out_sift", "masked_out_surf", "outside", "kept_sift", "kept_surf"):
+        mask_info[k] = [int(getattr(c, k)) for c in counts]
+    if mask_mode == "tracks" and any(has_mask):
+        keep = T.filter_marked(tt.offsets, np.stack([tt.view, tt.feat], axis=1), marks, has_mask).astype(bool)
+        if not keep.all():
+            kept_f = keep[tt.track_of]
+            offsets = np.concatenate([[0], np.cumsum(np.diff(tt.offsets)[keep])]).astype(np.int64)
+            tt = TrackTable.from_mve(offsets, np.stack([tt.view[kept_f], tt.feat[kept_f]], axis=1), norms, width[0], V)
+            tcol = tcol[keep]
+            mask_info["tracks_dropped"] = int((~keep).sum())
+    info["mask"] = mask_info
+    if feature_colors:
+        starts = np.concatenate([[0], np.cumsum([len(p) for p in pixel_rgb])]).astype(np.int64)
+        info["feature_rgb"] = np.concatenate(pixel_rgb)[starts[tt.view] + tt.feat]
+    return tt, tcol, info
 
 
 def _match_and_build(V, upload, sizes, image_width, matcher, device, verify, timings, pairs, options, colors):
@@ -1054,11 +1103,13 @@ def camera_to_world_matrices(model, cam_params):
     return out
 
 
-def save_project(res: Result, model, folder, image_names=None):
+def save_project(res: Result, model, folder, image_names=None, feature_rgb=None):
     """The files orthosfm::reconstruct leaves in the project folder (reconstruct.cpp:125,
     :160, :168, :290), written through the C ABI of the text formats: tracks.txt (all
     tracks, as built), cameras.txt (aligned cameras), sparse_cloud.ply (surviving tracks
-    with a point), time_measurements.txt."""
+    with a point), time_measurements.txt.  feature_rgb: uint8 [num_features, 3] in the
+    table's feature order (tracks_from_images' info["feature_rgb"]), the colours that
+    propagateColorsToTracks gives the features before the reference writes them; None: zeros."""
     from . import formats as F
     os.makedirs(folder, exist_ok=True)
     tt = res.tracks
@@ -1068,6 +1119,11 @@ def save_project(res: Result, model, folder, image_names=None):
     feats["global_feature_id"] = 32768 * tt.view.astype(np.int64) + tt.feat
     feats["x"] = tt.xy[:, 0]
     feats["y"] = tt.xy[:, 1]
+    if feature_rgb is not None:
+        rgb = np.asarray(feature_rgb)
+        if rgb.shape != (tt.view.shape[0], 3):
+            raise ValueError(f"save_project: feature_rgb {rgb.shape}, the table has {tt.view.shape[0]} features")
+        feats["r"], feats["g"], feats["b"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
     F.save_tracks_to_file_native(tt.offsets, feats, os.path.join(folder, "tracks.txt"))
     names = image_names or ["view_%04d" % v for v in range(tt.num_views)]
     al = list(res.aligned_views)

@@ -133,6 +133,28 @@ def feature_table(track_offsets, track_features, norm_positions, image_width, wa
     return view, feat, xy, track_of, by_view, view_start
 
 
+def filter_marked(track_offsets, track_features, marks, has_mask):
+    """osfm_tracks_filter_marked (filterTracksWithMasks): keep uint8 [num_tracks], 1 where every feature of the track
+    that lies in a view with a mask is masked in.  marks[v]: view v's uint8 marks (ViewFrontEnd.download_marks);
+    has_mask[v]: whether view v has a mask."""
+    offs = np.ascontiguousarray(track_offsets, dtype=np.int64)
+    tf = np.ascontiguousarray(track_features, dtype=np.int32).reshape(-1, 2)
+    V = len(marks)
+    starts = np.concatenate([[0], np.cumsum([len(m) for m in marks])]).astype(np.int64)
+    allm = np.ascontiguousarray(np.concatenate([np.asarray(m, np.uint8) for m in marks]) if V else np.zeros(0, np.uint8))
+    has = np.ascontiguousarray(np.asarray(has_mask, dtype=np.uint8).reshape(-1))
+    if has.shape[0] != V:
+        raise ValueError("filter_marked: one has_mask flag per view")
+    nt = offs.shape[0] - 1
+    keep = np.zeros(nt, np.uint8)
+    kept = C.c_int64()
+    capi.check(capi.lib.osfm_tracks_filter_marked(
+        C.c_int64(nt), offs.ctypes.data, tf.ctypes.data if tf.size else None, C.c_int32(V), starts.ctypes.data,
+        allm.ctypes.data if allm.size else None, has.ctypes.data if V else None, keep.ctypes.data if nt else None, C.byref(kept)))
+    assert int(keep.sum()) == kept.value
+    return keep
+
+
 _SELECT_BUFFERS = threading.local()      # per thread: the slices a call returns are valid until the SAME thread's next call
 
 
