@@ -652,7 +652,9 @@ OSFM_API int osfm_scene_download(osfm_scene *s, uint8_t *alive_track, uint8_t *a
  * rule, the fallback) and why: INTEGRATION.md section 3. */
 typedef struct osfm_tk_options {
     int32_t sample_size;        /* 10     tracks per hypothesis, 4..32 (tomasi_kanade.cpp:208) */
-    int32_t max_iterations;     /* 0      0: floor(log(1 - probability) / log(1 - inlier_ratio^sample_size)) = 241 (:212) */
+    int32_t max_iterations;     /* 0      0: floor(log(1 - probability) / log(1 - inlier_ratio^sample_size)) = 241 (:212),
+                                 *        held to 1 .. 2^20: at least one hypothesis runs (point 11);
+                                 *        at most 2^20 may be asked for */
     double probability;         /* 0.999  :209 */
     double inlier_ratio;        /* 0.7    :210 */
     int32_t min_consensus;      /* 25     tracks outside the sample that must support a model (:221) */

@@ -727,6 +727,8 @@ int tk_check_options(const osfm_tk_options *opts, int num_cameras, osfm_tk_optio
     }
     int H = out->max_iterations;
     if (H == 0) {
+        // the reference's count (:212), held to 1 .. 2^20 (point 11): a quotient below one
+        // means that one sample already reaches the probability, not that none is needed
         const double h = floor(log(1.0 - out->probability) / log(1.0 - pow(out->inlier_ratio, (double)out->sample_size)));
         H = h < 1.0 ? 1 : (h > (double)(1 << 20) ? (1 << 20) : (int)h);
     }

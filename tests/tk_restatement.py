@@ -1,14 +1,15 @@
 """The Tomasi-Kanade RANSAC initial alignment of a camera group, restated in numpy.
 
 A float64 statement of INTEGRATION.md section 3 (robustlyEstimateTomasiKanadeFactorization,
-src/algorithms/tomasi_kanade.cpp:193-370, with the ten departures listed there), written from that
+src/algorithms/tomasi_kanade.cpp:193-370, with the eleven departures listed there), written from that
 text and the reference -- not from the kernels -- with numpy.linalg.eigh / solve where the library
 runs Jacobi sweeps and an elimination of its own.  tests/test_tk_cases_cpu.py shows on it that the
 cases of tests/tk_cases.py are fit to judge a kernel; tests/test_tk_gpu.py holds osfm_tk_align and
 osfm_tk_resolve_ambiguity to it.
 
 `align(..., detail=True)` also returns what the CPU test bounds: per hypothesis the margins to every
-threshold and the conditioning of the two eigen-problems.
+threshold and the conditioning of the two eigen-problems, and the same for the factorisation of all
+tracks where the fallback runs (detail["fallback"]).
 """
 import math
 from dataclasses import dataclass, field
@@ -43,10 +44,15 @@ def sample(seed, group, it, n, size):
     return out
 
 
+MAX_ITERATIONS = 1 << 20
+
+
 def num_iterations(max_iterations=0, probability=0.999, inlier_ratio=0.7, sample_size=10):
+    """Point 11: the reference's formula (:212), held to 1 .. 2^20 hypotheses."""
     if max_iterations > 0:
         return int(max_iterations)
-    return int(math.log(1.0 - probability) / math.log(1.0 - inlier_ratio ** sample_size))
+    h = math.floor(math.log(1.0 - probability) / math.log(1.0 - inlier_ratio ** sample_size))
+    return int(min(max(h, 1), MAX_ITERATIONS))
 
 
 def normalise(xy, width, height):
@@ -170,6 +176,23 @@ class Result:
     detail: dict = field(default_factory=dict)
 
 
+def _conditioning(d, m):
+    """Folds the eigenvalues of one factorisation into the detail dictionary d.  A Gram matrix without a
+    positive third eigenvalue has no finite w1 / w3 and no gap to speak of: its |w3| / w1 (0 for the zero
+    matrix) goes to d["rank_ratio"], which the degenerate cases bound instead."""
+    w = m.gram_w
+    d["rank_ratio"].append(abs(w[2]) / w[0] if w[0] > 0 else 0.0)
+    d["gram_cond"] = max(d["gram_cond"], w[0] / w[2] if w[2] > 0 else np.inf)
+    if len(w) > 3 and w[0] > 0:
+        d["gram_gap"] = min(d["gram_gap"], (w[2] - w[3]) / w[0])
+    if m.metric_w is not None:
+        d["metric_ratio"].append(m.metric_w[0] / m.metric_w[2])
+
+
+def _new_detail():
+    return {"threshold_margin": np.inf, "metric_ratio": [], "rank_ratio": [], "gram_cond": 0.0, "gram_gap": np.inf}
+
+
 def align(xy, width, height, seed=0, group_id=0, sample_size=10, max_iterations=0, probability=0.999,
           inlier_ratio=0.7, min_consensus=25, max_error_px=3.0, detail=False):
     xy = np.asarray(xy, dtype=np.float64)
@@ -182,19 +205,13 @@ def align(xy, width, height, seed=0, group_id=0, sample_size=10, max_iterations=
     xn = normalise(xy, width, height)
     H = num_iterations(max_iterations, probability, inlier_ratio, sample_size)
     res.iterations = H
-    d = {"threshold_margin": np.inf, "usable_margin": np.inf, "metric_ratio": [], "gram_cond": 0.0,
-         "gram_gap": np.inf, "ranking": []}
+    d = dict(_new_detail(), usable_margin=np.inf, ranking=[], fallback=None)
     supported = []
     for it in range(H):
         s = sample(seed, group_id, it, N, sample_size)
         m = factorise(xn[s])
         if detail:
-            w = m.gram_w
-            d["gram_cond"] = max(d["gram_cond"], w[0] / w[2] if w[2] > 0 else np.inf)
-            if len(w) > 3:
-                d["gram_gap"] = min(d["gram_gap"], (w[2] - w[3]) / w[0])
-            if m.metric_w is not None:
-                d["metric_ratio"].append(m.metric_w[0] / m.metric_w[2])
+            _conditioning(d, m)
         if not m.ok:
             continue
         ok, margin = usable(m.basis_1)
@@ -211,21 +228,26 @@ def align(xy, width, height, seed=0, group_id=0, sample_size=10, max_iterations=
         if nc >= min_consensus:
             members = consensus | in_sample
             mean = err[members].sum() / (int(members.sum()) * C)                # point 7
-            supported.append((-nc, mean, it, m, members))
+            # (detail) where in draw order the sample holds tracks that miss the bound under their own model
+            misses = [k for k, t in enumerate(s) if not (err[t] <= max_error_px).all()]
+            supported.append((-nc, mean, it, m, members, misses))
     res.supported_models = len(supported)
     if supported:
         supported.sort(key=lambda r: r[:3])
-        nc, mean, it, m, members = supported[0]
+        nc, mean, it, m, members, d["winner_sample_misses"] = supported[0]
         res.status, res.best_iteration, res.num_inliers, res.mean_error_px = STATUS_RANSAC, it, int(members.sum()), mean
         res.basis_1, res.basis_2, res.offsets, res.inlier = m.basis_1, m.basis_2, m.offsets, members
         d["ranking"] = [(-r[0], r[1], r[2]) for r in supported[:2]]
     else:
         # point 9: the factorisation of all N given tracks; the tracks it reprojects within the bound are its inliers
         m = factorise(xn)
+        d["fallback"] = _new_detail()
+        _conditioning(d["fallback"], m)
         if not m.ok:
             res.status = STATUS_DEGENERATE
         else:
             err = reprojection_errors(m.basis_1, m.offsets, xn, width, height)
+            d["fallback"]["threshold_margin"] = np.abs(err - max_error_px).min()
             members = (err <= max_error_px).all(axis=1)
             res.status, res.num_inliers = STATUS_FALLBACK, int(members.sum())
             res.mean_error_px = err[members].sum() / (res.num_inliers * C) if res.num_inliers else 0.0
