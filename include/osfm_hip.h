@@ -41,7 +41,10 @@ OSFM_API const char *osfm_last_error(void);
  * 100: rounds 1-3; 101: osfm_ba_summary.flow_fallbacks, osfm_match_stats.surf_*; 102: one observation per camera
  * and point enforced, osfm_scene_set_cameras,
  * osfm_ba_summary.order_arcs / chain_blocks*.  New entries and new structs (the view front end, its marks) leave it alone:
- * nothing that a caller built against 102 reads or writes has changed. */
+ * nothing that a caller built against 102 reads or writes has changed.  osfm_match_options has since got
+ * ransac_model / ransac_refit appended, and the library READS that struct: the three entries that take it are bound
+ * under new symbol names by this header (see below it), and the symbols a caller built against the earlier header
+ * binds keep the earlier, shorter layout.  Such a caller still runs correctly, so the version is still 102. */
 #define OSFM_ABI_VERSION 102
 OSFM_API int osfm_version(void);
 /* Number of visible HIP devices (0 when there is none). */
@@ -140,6 +143,11 @@ OSFM_API int osfm_ransac_selfcheck(int mode, uint64_t *counters);
  * exhaustive in both (CascadeHashing inherits it). */
 #define OSFM_MATCHER_EXHAUSTIVE 0
 #define OSFM_MATCHER_CASCADE_HASHING 1
+/* Model of the geometric verification (osfm_match_options.ransac_model).  FUNDAMENTAL: the reference's RansacFundamental
+ * (8-point samples, a general fundamental matrix).  AFFINE: the affine fundamental matrix of two orthographic views
+ * (4-point samples, one least-squares refit), see osfm_ransac_affine. */
+#define OSFM_RANSAC_FUNDAMENTAL 0
+#define OSFM_RANSAC_AFFINE 1
 
 typedef struct osfm_match_options {
     float sift_lowe_ratio;          /* 0.8f   matching_base.h:27 */
@@ -175,7 +183,20 @@ typedef struct osfm_match_options {
      * per-view forms.
      * Results are identical either way. */
     int32_t special_kernel_max;
+    /* Model of the geometric verification: OSFM_RANSAC_FUNDAMENTAL (default) or OSFM_RANSAC_AFFINE; any other value
+     * is OSFM_E_ARG at create.  Everything around the estimator (the max(8, min_matching_inliers) gate, the
+     * statuses, the lists) is the same in both. */
+    int32_t ransac_model;
+    int32_t ransac_refit;           /* 1      affine model only: osfm_ransac_affine_options.refit */
 } osfm_match_options;
+
+/* The entries that take an osfm_match_options are bound as *_v2 symbols: the struct grew by ransac_model and
+ * ransac_refit, and the library cannot tell a shorter struct from its caller.  The library keeps the symbols
+ * osfm_match_options_default / osfm_match_create / osfm_match_create_multi for binaries built against the header
+ * before that: they write and read the struct up to special_kernel_max and take the defaults for the rest. */
+#define osfm_match_options_default osfm_match_options_default_v2
+#define osfm_match_create osfm_match_create_v2
+#define osfm_match_create_multi osfm_match_create_multi_v2
 
 OSFM_API int osfm_match_options_default(osfm_match_options *opts);
 
@@ -304,7 +325,9 @@ typedef struct osfm_pair_result {
  * With opts.geometric_verification the call continues through RANSAC-F
  * (bundler_matching.cc:194-219): the list of a pair then holds its num_inliers
  * inlier correspondences (TwoViewMatching::matches) and pairs with fewer than
- * max(8, min_matching_inliers) inliers are OSFM_PAIR_REJECTED_INLIERS.
+ * max(8, min_matching_inliers) inliers are OSFM_PAIR_REJECTED_INLIERS.  With
+ * opts.ransac_model = OSFM_RANSAC_AFFINE the estimator is osfm_ransac_affine's
+ * in the place of RANSAC-F; everything around it is the same.
  */
 OSFM_API int osfm_match_all(osfm_matcher *m, const osfm_pair *pairs,
     int num_pairs, osfm_pair_result *results, int32_t *corr,
@@ -370,6 +393,34 @@ OSFM_API int osfm_ransac_options_default(osfm_ransac_options *o);
 OSFM_API int osfm_ransac_fundamental(int device, const float *pos1, int n1, const float *pos2, int n2,
     const int32_t *corr, int k, const osfm_ransac_options *opts, uint64_t pair_id,
     int32_t *inliers, int32_t *num_inliers, double *F);
+
+/* Verification of a pair of ORTHOGRAPHIC views: RANSAC over affine fundamental matrices (no counterpart in the
+ * reference).  Two orthographic views are related by x2^T F_A x1 = a x2 + b y2 + c x1 + d y1 + e = 0, F_A =
+ * [0 0 a; 0 0 b; c d e]: 4 degrees of freedom, 4 matches per sample, and the Sampson distance that
+ * osfm_ransac_fundamental thresholds is exact for it (its denominator is a^2 + b^2 + c^2 + d^2).  refit != 0: when the
+ * winner has at least 5 inliers, F_A is fitted once more to all of them by least squares (smallest eigenvector of the
+ * scatter of (x2, y2, x1, y1)); the refit replaces the winner when it has at least as many inliers. */
+typedef struct osfm_ransac_affine_options {
+    int32_t max_iterations;   /* 1000 */
+    int32_t refit;            /* 1 */
+    double threshold;         /* 0.0015 */
+    uint64_t seed;
+} osfm_ransac_affine_options;
+OSFM_API int osfm_ransac_affine_options_default(osfm_ransac_affine_options *o);
+
+typedef struct osfm_ransac_affine_result {
+    int32_t best_iteration;   /* iteration of the winning sample (-1: no hypothesis had an inlier) */
+    int32_t ransac_inliers;   /* its inlier count, before the refit */
+    int32_t refit_ran;        /* 1: the refit was computed (refit != 0 and ransac_inliers >= 5) */
+    int32_t refit_accepted;   /* 1: F and the inlier list are the refit's */
+} osfm_ransac_affine_result;
+
+/* Arguments as osfm_ransac_fundamental; *num_inliers = -1 for k < 4 (nothing else is written then).  F (may be NULL)
+ * receives F_A as 9 doubles, row major, in the layout above, scaled to a^2 + b^2 + c^2 + d^2 = 1 (up to rounding
+ * after a refit): whatever reads the F of osfm_ransac_fundamental can read it.  result may be NULL. */
+OSFM_API int osfm_ransac_affine(int device, const float *pos1, int n1, const float *pos2, int n2,
+    const int32_t *corr, int k, const osfm_ransac_affine_options *opts, uint64_t pair_id,
+    int32_t *inliers, int32_t *num_inliers, double *F, osfm_ransac_affine_result *result);
 
 /* ====================================================================== */
 /* (B) Bundle adjustment                                                   */

@@ -35,6 +35,7 @@ class OsfmError(RuntimeError):
 
 OK, E_ARG, E_DEVICE, E_RANGE, E_CAPACITY, E_STATE, E_NUMERIC, E_IO = 0, -1, -2, -3, -4, -5, -6, -7
 MATCHER_EXHAUSTIVE, MATCHER_CASCADE_HASHING = 0, 1
+RANSAC_FUNDAMENTAL, RANSAC_AFFINE = 0, 1
 PAIR_MATCHED, PAIR_REJECTED_LOWRES, PAIR_REJECTED_COUNT, PAIR_SKIPPED_EMPTY, PAIR_REJECTED_INLIERS = 0, 1, 2, 3, 4
 
 
@@ -47,12 +48,25 @@ class MatchOptions(C.Structure):
                 ("geometric_verification", C.c_int32), ("ransac_max_iterations", C.c_int32),
                 ("ransac_threshold", C.c_double), ("min_matching_inliers", C.c_int32),
                 ("matcher_type", C.c_int32), ("ransac_seed", C.c_uint64),
-                ("cascade_keep_empty_blocks", C.c_int32), ("special_kernel_max", C.c_int32)]
+                ("cascade_keep_empty_blocks", C.c_int32), ("special_kernel_max", C.c_int32),
+                ("ransac_model", C.c_int32), ("ransac_refit", C.c_int32)]
 
 
 class RansacOptions(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("reserved", C.c_int32),
                 ("threshold", C.c_double), ("seed", C.c_uint64)]
+
+
+class RansacAffineOptions(C.Structure):
+    """osfm_ransac_affine_options"""
+    _fields_ = [("max_iterations", C.c_int32), ("refit", C.c_int32),
+                ("threshold", C.c_double), ("seed", C.c_uint64)]
+
+
+class RansacAffineResult(C.Structure):
+    """osfm_ransac_affine_result"""
+    _fields_ = [("best_iteration", C.c_int32), ("ransac_inliers", C.c_int32),
+                ("refit_ran", C.c_int32), ("refit_accepted", C.c_int32)]
 
 
 class Pair(C.Structure):
@@ -240,7 +254,7 @@ EXPORTS = [
     "osfm_match_options_default", "osfm_match_create", "osfm_match_create_multi", "osfm_match_get_devices", "osfm_match_destroy",
     "osfm_quantize_sift", "osfm_quantize_surf",
     "osfm_match_set_view", "osfm_match_set_view_float", "osfm_match_view_size", "osfm_match_expect_pairs", "osfm_match_set_positions",
-    "osfm_ransac_options_default", "osfm_ransac_fundamental",
+    "osfm_ransac_options_default", "osfm_ransac_fundamental", "osfm_ransac_affine_options_default", "osfm_ransac_affine",
     "osfm_match_pair", "osfm_match_pair_lowres", "osfm_match_twoway", "osfm_match_all",
     "osfm_pair_from_index", "osfm_match_get_stats", "osfm_match_get_shard_stats", "osfm_match_get_cascade_hashes",
     "osfm_ba_options_default", "osfm_ba_small_limits", "osfm_ba_solve", "osfm_ba_reprojection_errors",
@@ -276,6 +290,11 @@ lib.osfm_last_error.restype = C.c_char_p
 lib.osfm_version.restype = C.c_int
 # include/osfm_hip.h OSFM_ABI_VERSION: the structs below mirror THAT header, and the library writes them in full
 ABI_VERSION = 102
+# The header binds the entries that take an osfm_match_options to these symbols (the struct grew; the plain names keep
+# the earlier layout for binaries built before that): this module and matching.py call them by these names.
+for _name in ("osfm_match_options_default_v2", "osfm_match_create_v2", "osfm_match_create_multi_v2"):
+    if not hasattr(lib, _name):
+        raise ImportError(f"libosfm_hip.so lacks {_name} (rebuild: make -C orthosfm_amd/csrc)")
 if lib.osfm_version() != ABI_VERSION and os.environ.get("OSFM_ALLOW_ABI_MISMATCH") != "1":
     raise ImportError(f"libosfm_hip.so reports ABI version {lib.osfm_version()}, orthosfm_amd/capi.py mirrors {ABI_VERSION} "
                       "(rebuild: make -C orthosfm_amd/csrc; experiments with an older build: OSFM_ALLOW_ABI_MISMATCH=1)")
@@ -395,7 +414,7 @@ def library_memory() -> MemoryReport:
 
 def default_match_options() -> MatchOptions:
     o = MatchOptions()
-    check(lib.osfm_match_options_default(C.byref(o)))
+    check(lib.osfm_match_options_default_v2(C.byref(o)))      # the symbol the header binds: MatchOptions in full
     return o
 
 

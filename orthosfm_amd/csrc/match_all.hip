@@ -7,6 +7,7 @@
 
 #include "match_internal.h"
 #include "ransac_kernels.h"
+#include "ransac_affine.h"
 
 namespace osfm {
 
@@ -65,7 +66,8 @@ int compact_chunk(osfm_matcher *m, const ChunkLists &h, int n, int64_t chunk_cor
     return OSFM_OK;
 }
 
-// RANSAC-F on the device-resident lists of a chunk (bundler_matching.cc:194-219): entry k of the chunk is pair
+// RANSAC-F (or, with ransac_model OSFM_RANSAC_AFFINE, the affine RANSAC of ransac_affine.hip) on the device-resident
+// lists of a chunk (bundler_matching.cc:194-219): entry k of the chunk is pair
 // idx[k] with counts[k] correspondences.  Pairs with enough inliers keep them, at corr + 2 * *written_out on.
 int verify_chunk(osfm_matcher *m, const osfm_pair *pairs, const int *idx, int n, const std::vector<int32_t> &counts,
     const ChunkLists &h, int64_t chunk_corr, osfm_pair_result *results, int32_t *corr, int64_t capacity,
@@ -100,10 +102,15 @@ int verify_chunk(osfm_matcher *m, const osfm_pair *pairs, const int *idx, int n,
         jobs.push_back(j); job_pair.push_back(k);
     }
     const size_t jobs_bytes = (jobs.size() * sizeof(RansacJob) + 255) / 256 * 256;
-    OSFM_RETURN_IF(m->d_jobs.reserve(jobs_bytes + ransac_scratch_bytes((int)jobs.size())));
+    const bool affine = o.ransac_model == OSFM_RANSAC_AFFINE;
+    OSFM_RETURN_IF(m->d_jobs.reserve(jobs_bytes + (affine ? affine_scratch_bytes((int)jobs.size()) : ransac_scratch_bytes((int)jobs.size()))));
     OSFM_HIP_CHECK(hipMemcpyAsync(m->d_jobs.ptr, jobs.data(), jobs.size() * sizeof(RansacJob), hipMemcpyHostToDevice, s));
-    launch_ransac(m->d_jobs.as<RansacJob>(), (int)jobs.size(), o.ransac_max_iterations, o.ransac_threshold,
-        o.ransac_seed, static_cast<char *>(m->d_jobs.ptr) + jobs_bytes, s);
+    if (affine)
+        launch_ransac_affine(m->d_jobs.as<RansacJob>(), (int)jobs.size(), o.ransac_max_iterations, o.ransac_threshold,
+            o.ransac_refit, o.ransac_seed, static_cast<char *>(m->d_jobs.ptr) + jobs_bytes, nullptr, s);
+    else
+        launch_ransac(m->d_jobs.as<RansacJob>(), (int)jobs.size(), o.ransac_max_iterations, o.ransac_threshold,
+            o.ransac_seed, static_cast<char *>(m->d_jobs.ptr) + jobs_bytes, s);
     OSFM_HIP_CHECK(hipGetLastError());
     std::vector<int32_t> h_cnt(jobs.size());
     OSFM_HIP_CHECK(hipMemcpyAsync(h_cnt.data(), m->d_inl_count.ptr, jobs.size() * 4, hipMemcpyDeviceToHost, s));

@@ -5,11 +5,13 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 #include "match_internal.h"
 #include "cashash_kernels.h"
 #include "ransac_kernels.h"
+#include "ransac_affine.h"
 #include "view_front.h"
 
 namespace osfm {
@@ -119,6 +121,8 @@ int osfm_match_options_default(osfm_match_options *o)
     o->ransac_seed = 0;
     o->cascade_keep_empty_blocks = 0;
     o->special_kernel_max = 0;
+    o->ransac_model = OSFM_RANSAC_FUNDAMENTAL;
+    o->ransac_refit = 1;
     return OSFM_OK;
 }
 
@@ -126,6 +130,10 @@ int osfm_match_create(int device, int num_views, const osfm_match_options *opts,
 {
     if (!out || num_views < 0) { set_error("match_create: bad arguments"); return OSFM_E_ARG; }
     *out = nullptr;
+    if (opts && opts->ransac_model != OSFM_RANSAC_FUNDAMENTAL && opts->ransac_model != OSFM_RANSAC_AFFINE) {
+        set_error("match_create: ransac_model %d", opts->ransac_model);
+        return OSFM_E_ARG;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("match_create: no HIP device available (this backend has no CPU fallback)");
@@ -179,6 +187,10 @@ int osfm_match_create_multi(const int *device_ids, int num_devices, int num_view
 {
     if (!out || !device_ids || num_devices < 1 || num_views < 0) { set_error("match_create_multi: bad arguments"); return OSFM_E_ARG; }
     *out = nullptr;
+    if (opts && opts->ransac_model != OSFM_RANSAC_FUNDAMENTAL && opts->ransac_model != OSFM_RANSAC_AFFINE) {
+        set_error("match_create_multi: ransac_model %d", opts->ransac_model);
+        return OSFM_E_ARG;
+    }
     struct Owner { osfm_matcher *p; ~Owner() { if (p) osfm_match_destroy(p); } } owner{(g_ledger.live_matchers++, new osfm_matcher())};
     osfm_matcher *m = owner.p;
     m->device = device_ids[0];
@@ -452,6 +464,62 @@ int osfm_ransac_fundamental(int device, const float *pos1, int n1, const float *
     return OSFM_OK;
 }
 
+int osfm_ransac_affine_options_default(osfm_ransac_affine_options *o)
+{
+    if (!o) { set_error("ransac_affine_options_default: null"); return OSFM_E_ARG; }
+    o->max_iterations = 1000; o->refit = 1; o->threshold = 0.0015; o->seed = 0;
+    return OSFM_OK;
+}
+
+int osfm_ransac_affine(int device, const float *pos1, int n1, const float *pos2, int n2,
+    const int32_t *corr, int k, const osfm_ransac_affine_options *opts, uint64_t pair_id,
+    int32_t *inliers, int32_t *num_inliers, double *F, osfm_ransac_affine_result *result)
+{
+    if (n1 < 0 || n2 < 0 || k < 0 || !num_inliers || (k > 0 && (!pos1 || !pos2 || !corr || !inliers))) {
+        set_error("ransac_affine: bad argument"); return OSFM_E_ARG;
+    }
+    for (int i = 0; i < k; ++i)
+        if (corr[2 * i] < 0 || corr[2 * i] >= n1 || corr[2 * i + 1] < 0 || corr[2 * i + 1] >= n2) {
+            set_error("ransac_affine: correspondence %d out of range", i); return OSFM_E_ARG;
+        }
+    osfm_ransac_affine_options o;
+    if (opts) o = *opts; else osfm_ransac_affine_options_default(&o);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_error("ransac_affine: no HIP device available (this backend has no CPU fallback)");
+        return OSFM_E_DEVICE;
+    }
+    if (device < 0 || device >= ndev) { set_error("ransac_affine: bad device"); return OSFM_E_ARG; }
+    OSFM_HIP_CHECK(hipSetDevice(device));
+    if (k < 4) { *num_inliers = -1; return OSFM_OK; }
+    DeviceBuffer d1, d2, dc, di, dn, df, dj, dr;
+    struct Rel { DeviceBuffer *b[8]; ~Rel() { for (auto *x : b) x->release(); } } rel{{&d1, &d2, &dc, &di, &dn, &df, &dj, &dr}};
+    OSFM_RETURN_IF(d1.reserve((size_t)n1 * 8)); OSFM_RETURN_IF(d2.reserve((size_t)n2 * 8));
+    OSFM_RETURN_IF(dc.reserve((size_t)k * 8)); OSFM_RETURN_IF(di.reserve((size_t)k * 4));
+    OSFM_RETURN_IF(dn.reserve(16)); OSFM_RETURN_IF(df.reserve(72)); OSFM_RETURN_IF(dr.reserve(sizeof(osfm_ransac_affine_result)));
+    OSFM_RETURN_IF(dj.reserve(256 + affine_scratch_bytes(1)));       // the job, then the kernel's scratch
+    OSFM_HIP_CHECK(hipMemcpy(d1.ptr, pos1, (size_t)n1 * 8, hipMemcpyHostToDevice));
+    OSFM_HIP_CHECK(hipMemcpy(d2.ptr, pos2, (size_t)n2 * 8, hipMemcpyHostToDevice));
+    OSFM_HIP_CHECK(hipMemcpy(dc.ptr, corr, (size_t)k * 8, hipMemcpyHostToDevice));
+    RansacJob job;
+    memset(&job, 0, sizeof(job));
+    job.pos1 = d1.as<float>(); job.pos2 = d2.as<float>(); job.corr = dc.as<int32_t>(); job.k = k;
+    job.pair_id = pair_id; job.inliers_out = di.as<int32_t>(); job.count_out = dn.as<int32_t>();
+    job.F_out = df.as<double>();
+    OSFM_HIP_CHECK(hipMemcpy(dj.ptr, &job, sizeof(job), hipMemcpyHostToDevice));
+    launch_ransac_affine(dj.as<RansacJob>(), 1, o.max_iterations, o.threshold, o.refit, o.seed, static_cast<char *>(dj.ptr) + 256,
+        dr.as<osfm_ransac_affine_result>(), nullptr);
+    OSFM_HIP_CHECK(hipGetLastError());
+    OSFM_HIP_CHECK(hipDeviceSynchronize());
+    int32_t cnt = 0;
+    OSFM_HIP_CHECK(hipMemcpy(&cnt, dn.ptr, 4, hipMemcpyDeviceToHost));
+    *num_inliers = cnt;
+    if (cnt > 0) OSFM_HIP_CHECK(hipMemcpy(inliers, di.ptr, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+    if (F) OSFM_HIP_CHECK(hipMemcpy(F, df.ptr, 72, hipMemcpyDeviceToHost));
+    if (result) OSFM_HIP_CHECK(hipMemcpy(result, dr.ptr, sizeof(*result), hipMemcpyDeviceToHost));
+    return OSFM_OK;
+}
+
 int osfm_match_pair(osfm_matcher *m, int view_1, int view_2, int32_t *m12, int32_t *len12,
     int32_t *m21, int32_t *len21)
 {
@@ -582,6 +650,44 @@ int osfm_match_get_stats(const osfm_matcher *m, osfm_match_stats *out)
     }
     *out = m->stats;
     return OSFM_OK;
+}
+
+// The symbols a binary built against the header before osfm_match_options grew (ransac_model, ransac_refit) binds: the
+// struct as it was then, up to special_kernel_max; the rest takes its defaults.  The header binds today's callers to
+// the *_v2 definitions above.
+#undef osfm_match_options_default
+#undef osfm_match_create
+#undef osfm_match_create_multi
+static constexpr size_t kOptionsBytesBefore = offsetof(osfm_match_options, ransac_model);
+static_assert(kOptionsBytesBefore == 80, "the layout binaries built against the earlier header pass");
+
+static osfm_match_options options_from_before(const void *opts)
+{
+    osfm_match_options o;
+    memset(&o, 0, sizeof(o));                 // its padding too: osfm_match_options_default copies it out
+    osfm_match_options_default_v2(&o);
+    if (opts) memcpy(&o, opts, kOptionsBytesBefore);
+    return o;
+}
+
+OSFM_API int osfm_match_options_default(void *opts)
+{
+    if (!opts) { set_error("options_default: null"); return OSFM_E_ARG; }
+    const osfm_match_options o = options_from_before(nullptr);
+    memcpy(opts, &o, kOptionsBytesBefore);
+    return OSFM_OK;
+}
+
+OSFM_API int osfm_match_create(int device, int num_views, const void *opts, osfm_matcher **out)
+{
+    const osfm_match_options o = options_from_before(opts);
+    return osfm_match_create_v2(device, num_views, &o, out);
+}
+
+OSFM_API int osfm_match_create_multi(const int *device_ids, int num_devices, int num_views, const void *opts, osfm_matcher **out)
+{
+    const osfm_match_options o = options_from_before(opts);
+    return osfm_match_create_multi_v2(device_ids, num_devices, num_views, &o, out);
 }
 
 }  // extern "C"

@@ -1,0 +1,438 @@
+// Geometric verification of a pair of ORTHOGRAPHIC views on the GPU: RANSAC over affine fundamental matrices
+//
+//         | 0 0 a |
+//   F_A = | 0 0 b |      x2^T F_A x1 = a x2 + b y2 + c x1 + d y1 + e = 0
+//         | c d e |
+//
+// from minimal samples of 4 matches, with the Sampson distance of the 8-point kernel (ransac_kernels.hip) as the
+// inlier test -- for F_A its denominator is the constant a^2 + b^2 + c^2 + d^2, so the distance is exact -- and one
+// least-squares refit on the winner's inliers.  The reference project has no such estimator (its RansacFundamental
+// is the 8-point one); the mode is opt-in (osfm_match_options.ransac_model, osfm_ransac_affine).
+//
+// Same job records, same counter-based sample stream, same split of a pair's hypotheses over kRansacSplit workgroups
+// with best-of-part slots and a last-arriver finish as ransac_kernel; no workgroup waits for another.  All arithmetic
+// is double precision in ONE operation order (this file is built without FMA contraction), restated operation for
+// operation in tests/affine_restatement.py, which the kernel equals bit for bit.  Everything a thread holds is
+// statically indexed (the elimination, the sample, the 4 x 4 Jacobi are unrolled on scalars): no scratch memory.
+#include "ransac_affine.h"
+#include "ransac_rand.h"
+#include "osfm_common.h"
+
+#include <algorithm>
+
+namespace osfm {
+
+// best (count, iteration, vector) of one part of a pair's hypotheses
+struct AffineSlot { int32_t count, iter; double v[5]; };
+
+namespace {
+
+// One hypothesis as the kernel holds it: v = (a, b, c, d, e), s = a^2 + b^2 + c^2 + d^2 and the two bounds of the
+// safe product tests, s thr^2 (1 -+ 2^-49) (sampson_below in ransac_kernels.hip has the argument).
+struct AffineHyp { double v[5], s, s_lo, s_hi; };
+
+__device__ __forceinline__ void affine_bounds(AffineHyp &h, double thr_lo, double thr_hi)
+{
+    h.s = ((h.v[0] * h.v[0] + h.v[1] * h.v[1]) + h.v[2] * h.v[2]) + h.v[3] * h.v[3];
+    h.s_lo = h.s * thr_lo;
+    h.s_hi = h.s * thr_hi;
+}
+
+// sampson(F_A, x1, y1, x2, y2) < thr2 of ransac_kernels.hip in its own order of operations, with the terms that F_A's
+// zeros remove left out: n = (x2 a + y2 b) + ((x1 c + y1 d) + e), the sum of squares is s.
+__device__ __forceinline__ bool
+affine_below(const AffineHyp &h, double x1, double y1, double x2, double y2, double thr2)
+{
+    double n = (x2 * h.v[0] + y2 * h.v[1]) + ((x1 * h.v[2] + y1 * h.v[3]) + h.v[4]);
+    n *= n;
+    if (n < h.s_lo) return true;                     // strict: s == 0 never passes here
+    if (n >= h.s_hi) return false;
+    return n / h.s < thr2;                           // the sliver, and NaN operands
+}
+
+__device__ __forceinline__ void swap_if(bool c, double &a, double &b)
+{
+    const double t = a;
+    a = c ? b : a;
+    b = c ? t : b;
+}
+
+__device__ __forceinline__ void sort2(int &a, int &b)
+{
+    const int lo = min(a, b), hi = max(a, b);
+    a = lo; b = hi;
+}
+
+// Null vector of the 4 x 5 system with rows (x2, y2, x1, y1, 1) by Gauss-Jordan elimination with full pivoting
+// (eight_point's scheme: the first largest modulus in row-major order is the pivot), scaled to a^2 + b^2 + c^2 +
+// d^2 = 1.  Row and column exchanges are selects over the statically indexed positions.  False, and v zero: a pivot
+// that is not > 0, or a = b = c = d = 0.
+__device__ __forceinline__ bool four_point(const double (&P)[4][4], double (&v)[5])
+{
+    double A[4][5];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) A[i][j] = P[i][j];
+        A[i][4] = 1.0;
+    }
+    int perm[5] = {0, 1, 2, 3, 4};
+    bool ok = true;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        int pr = r, pc = r;
+        double best = -1.0;
+#pragma unroll
+        for (int i = r; i < 4; ++i)
+#pragma unroll
+            for (int j = r; j < 5; ++j) {
+                const double m = fabs(A[i][j]);
+                if (m > best) { best = m; pr = i; pc = j; }
+            }
+        ok = ok && best > 0.0;
+        // (columns left of r are not read again in rows r and below)
+#pragma unroll
+        for (int i = r + 1; i < 4; ++i)
+#pragma unroll
+            for (int j = r; j < 5; ++j) swap_if(pr == i, A[r][j], A[i][j]);
+#pragma unroll
+        for (int j = r + 1; j < 5; ++j) {
+            const bool c = pc == j;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) swap_if(c, A[i][r], A[i][j]);
+            const int t = perm[r];
+            perm[r] = c ? perm[j] : perm[r];
+            perm[j] = c ? t : perm[j];
+        }
+        const double inv = 1.0 / A[r][r];
+#pragma unroll
+        for (int j = r + 1; j < 5; ++j) A[r][j] *= inv;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i == r) continue;
+            const double fct = A[i][r];
+#pragma unroll
+            for (int j = r + 1; j < 5; ++j) A[i][j] -= fct * A[r][j];
+        }
+    }
+    double f[5];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+        f[c] = 1.0;                                  // the free column, perm[4]
+#pragma unroll
+        for (int r = 0; r < 4; ++r) f[c] = perm[r] == c ? -A[r][4] : f[c];
+    }
+    const double s = ((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2]) + f[3] * f[3];
+    ok = ok && s > 0.0;
+    const double inv = 1.0 / sqrt(s);
+#pragma unroll
+    for (int c = 0; c < 5; ++c) v[c] = ok ? f[c] * inv : 0.0;
+    return ok;
+}
+
+// Eigenvectors of a symmetric 4 x 4 matrix by cyclic Jacobi, eig3_fixed of ransac_kernels.hip with one more row.
+__device__ __forceinline__ void eig4_fixed(double (&A)[4][4], double (&V)[4][4], double (&w)[4])
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        const double off = ((((fabs(A[0][1]) + fabs(A[0][2])) + fabs(A[0][3])) + fabs(A[1][2])) + fabs(A[1][3])) + fabs(A[2][3]);
+        if (off == 0.0) break;
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 4; ++q) {
+                if (A[p][q] == 0.0) continue;
+                const double th = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+                const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const double akp = A[k][p], akq = A[k][q];
+                    A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const double apk = A[p][k], aqk = A[q][k];
+                    A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const double vkp = V[k][p], vkq = V[k][q];
+                    V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq;
+                }
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = A[i][i];
+}
+
+// (x1, y1, x2, y2) of match i of a job
+__device__ __forceinline__ double4 load_match(const RansacJob &job, int i)
+{
+    const int a = job.corr[2 * i], b = job.corr[2 * i + 1];
+    return make_double4(job.pos1[2 * a], job.pos1[2 * a + 1], job.pos2[2 * b], job.pos2[2 * b + 1]);
+}
+
+// red[q * 256 + tid], q < N, holds a partial sum per thread: the fixed tree that leaves the totals in red[q * 256]
+template <int N>
+__device__ __forceinline__ void tree_sum(double *red, int tid)
+{
+    __syncthreads();
+    for (int st = 128; st >= 1; st >>= 1) {
+        if (tid < st) {
+#pragma unroll
+            for (int q = 0; q < N; ++q) red[q * 256 + tid] += red[q * 256 + tid + st];
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void
+ransac_affine_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_iterations, double thr2, int refit,
+    uint64_t seed, AffineSlot *__restrict__ slots, int32_t *__restrict__ done, osfm_ransac_affine_result *__restrict__ results)
+{
+    __shared__ double4 mpt[kAffineChunk];     // (x1, y1, x2, y2) of the staged matches; the partial sums of the refit
+    __shared__ int s_count[256], s_iter[256];
+    __shared__ double s_v[5];
+    __shared__ int s_wave[4], s_run, s_last, s_n;
+
+    const int jid = blockIdx.x / kRansacSplit, part = blockIdx.x % kRansacSplit;
+    const RansacJob job = jobs[jid];
+    const int k = job.k, tid = threadIdx.x;
+    if (k < 4) {
+        if (tid == 0 && part == 0) *job.count_out = -1;
+        return;
+    }
+    // this part's iterations: whole passes of 256 * kAffineHyp
+    constexpr int kPass = 256 * kAffineHyp;
+    const int per_part = ((max_iterations + kRansacSplit - 1) / kRansacSplit + kPass - 1) / kPass * kPass;
+    const int it_begin = part * per_part, it_end = min(max_iterations, it_begin + per_part);
+    const double thr_lo = thr2 * (1.0 - 1.7763568394002505e-15);     // 2^-49
+    const double thr_hi = thr2 * (1.0 + 1.7763568394002505e-15);
+    int best_count = 0, best_iter = 0x7fffffff;
+    double bestv[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+
+    for (int base = it_begin; base < it_end; base += kPass) {
+        AffineHyp H[kAffineHyp];
+        bool valid[kAffineHyp];
+        int cnt[kAffineHyp];
+#pragma unroll
+        for (int h = 0; h < kAffineHyp; ++h) {
+            const int it = base + h * 256 + tid;
+            valid[h] = false; cnt[h] = 0;
+#pragma unroll
+            for (int i = 0; i < 5; ++i) H[h].v[i] = 0.0;
+            if (it < it_end) {
+                // the first 4 distinct draws mod k, ascending
+                int i0 = -1, i1 = -1, i2 = -1, i3 = -1, n = 0;
+                for (uint64_t d = 0; n < 4; ++d) {
+                    const int v = (int)(ransac_rand(seed, job.pair_id, (uint64_t)it, d) % (uint64_t)k);
+                    if (v == i0 || v == i1 || v == i2) continue;
+                    if (n == 0) i0 = v; else if (n == 1) i1 = v; else if (n == 2) i2 = v; else i3 = v;
+                    ++n;
+                }
+                sort2(i0, i1); sort2(i2, i3); sort2(i0, i2); sort2(i1, i3); sort2(i1, i2);
+                const double4 m0 = load_match(job, i0), m1 = load_match(job, i1), m2 = load_match(job, i2), m3 = load_match(job, i3);
+                const double P[4][4] = { { m0.z, m0.w, m0.x, m0.y }, { m1.z, m1.w, m1.x, m1.y },
+                                         { m2.z, m2.w, m2.x, m2.y }, { m3.z, m3.w, m3.x, m3.y } };
+                valid[h] = four_point(P, H[h].v);
+            }
+            affine_bounds(H[h], thr_lo, thr_hi);
+        }
+        // inlier counts of this thread's hypotheses over all matches; every lane reads the same match
+        for (int c0 = 0; c0 < k; c0 += kAffineChunk) {
+            __syncthreads();
+            for (int i = tid; i < kAffineChunk && c0 + i < k; i += 256) mpt[i] = load_match(job, c0 + i);
+            __syncthreads();
+            const int lim = min(kAffineChunk, k - c0);
+            // invalid hypotheses (v zero: n = 0, s = 0, never below) are evaluated too: no divergence in the loop.
+            // Four matches per round: their LDS reads are issued together
+            int i = 0;
+            for (; i + 4 <= lim; i += 4) {
+                const double4 a0 = mpt[i], a1 = mpt[i + 1], a2 = mpt[i + 2], a3 = mpt[i + 3];
+#pragma unroll
+                for (int h = 0; h < kAffineHyp; ++h) {
+                    cnt[h] += affine_below(H[h], a0.x, a0.y, a0.z, a0.w, thr2) ? 1 : 0;
+                    cnt[h] += affine_below(H[h], a1.x, a1.y, a1.z, a1.w, thr2) ? 1 : 0;
+                    cnt[h] += affine_below(H[h], a2.x, a2.y, a2.z, a2.w, thr2) ? 1 : 0;
+                    cnt[h] += affine_below(H[h], a3.x, a3.y, a3.z, a3.w, thr2) ? 1 : 0;
+                }
+            }
+            for (; i < lim; ++i) {
+                const double4 a0 = mpt[i];
+#pragma unroll
+                for (int h = 0; h < kAffineHyp; ++h) cnt[h] += affine_below(H[h], a0.x, a0.y, a0.z, a0.w, thr2) ? 1 : 0;
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < kAffineHyp; ++h) {
+            const int it = base + h * 256 + tid;
+            // strictly more inliers wins; equal non-zero counts keep the earlier iteration
+            if (valid[h] && (cnt[h] > best_count || (cnt[h] == best_count && cnt[h] > 0 && it < best_iter))) {
+                best_count = cnt[h]; best_iter = it;
+#pragma unroll
+                for (int i = 0; i < 5; ++i) bestv[i] = H[h].v[i];
+            }
+        }
+    }
+    // block argmax: (count desc, iteration asc)
+    s_count[tid] = best_count; s_iter[tid] = best_iter;
+    __syncthreads();
+    for (int st = 128; st >= 1; st >>= 1) {
+        if (tid < st) {
+            const int c2 = s_count[tid + st], i2 = s_iter[tid + st];
+            if (c2 > s_count[tid] || (c2 == s_count[tid] && i2 < s_iter[tid])) { s_count[tid] = c2; s_iter[tid] = i2; }
+        }
+        __syncthreads();
+    }
+    int win_count = s_count[0], win_iter = s_iter[0];
+    if (best_count == win_count && best_iter == win_iter && win_count > 0) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) s_v[i] = bestv[i];
+    }
+    __syncthreads();
+    // this part's best into its slot; the last part to get here goes on with all of them
+    if (tid == 0) {
+        AffineSlot &mine = slots[(size_t)jid * kRansacSplit + part];
+        mine.count = win_count; mine.iter = win_iter;
+        for (int i = 0; i < 5; ++i) mine.v[i] = win_count > 0 ? s_v[i] : 0.0;
+        __threadfence();
+        s_last = atomicAdd(&done[jid], 1) == kRansacSplit - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    if (tid == 0) {
+        __threadfence();
+        int bc = 0, bi = 0x7fffffff, bp = -1;
+        for (int p = 0; p < kRansacSplit; ++p) {
+            const AffineSlot &sl = slots[(size_t)jid * kRansacSplit + p];
+            if (sl.count > bc || (sl.count == bc && sl.count > 0 && sl.iter < bi)) { bc = sl.count; bi = sl.iter; bp = p; }
+        }
+        s_count[0] = bc; s_iter[0] = bi;
+        for (int i = 0; i < 5; ++i) s_v[i] = bp >= 0 ? slots[(size_t)jid * kRansacSplit + bp].v[i] : 0.0;
+        done[jid] = 0;                 // ready for the next launch
+        s_run = 0; s_n = 0;
+    }
+    __syncthreads();
+    win_count = s_count[0]; win_iter = s_iter[0];
+    if (win_count == 0) {
+        if (tid == 0) {
+            *job.count_out = 0;
+            if (job.F_out) for (int i = 0; i < 9; ++i) job.F_out[i] = 0.0;
+            if (results) results[jid] = osfm_ransac_affine_result{-1, 0, 0, 0};
+        }
+        return;
+    }
+    AffineHyp W;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) W.v[i] = s_v[i];
+    affine_bounds(W, thr_lo, thr_hi);
+    const int lane = tid & 63, wave = tid >> 6;
+    int ran = 0, accepted = 0;
+    if (refit && win_count >= 5) {
+        // One least-squares refit on the winner's inliers: z = (x2, y2, x1, y1), the mean in a first pass, the scatter
+        // about it in a second, (a, b, c, d) the scatter's eigenvector of the smallest eigenvalue, e = -(a, b, c, d) . mean.
+        // Thread t adds matches t, t + 256, ... in order (a match that is no inlier adds +0), then a fixed tree over
+        // the 256 partial sums: the order is a function of k alone.
+        double *red = reinterpret_cast<double *>(mpt);
+        double z0 = 0.0, z1 = 0.0, z2 = 0.0, z3 = 0.0;
+        for (int i = tid; i < k; i += 256) {
+            const double4 m = load_match(job, i);
+            const bool in = affine_below(W, m.x, m.y, m.z, m.w, thr2);
+            z0 += in ? m.z : 0.0; z1 += in ? m.w : 0.0; z2 += in ? m.x : 0.0; z3 += in ? m.y : 0.0;
+        }
+        __syncthreads();               // the staged matches are not read again
+        red[0 * 256 + tid] = z0; red[1 * 256 + tid] = z1; red[2 * 256 + tid] = z2; red[3 * 256 + tid] = z3;
+        tree_sum<4>(red, tid);
+        const double cn = (double)win_count;
+        const double mu0 = red[0] / cn, mu1 = red[256] / cn, mu2 = red[512] / cn, mu3 = red[768] / cn;
+        __syncthreads();
+        double c00 = 0.0, c01 = 0.0, c02 = 0.0, c03 = 0.0, c11 = 0.0, c12 = 0.0, c13 = 0.0, c22 = 0.0, c23 = 0.0, c33 = 0.0;
+        for (int i = tid; i < k; i += 256) {
+            const double4 m = load_match(job, i);
+            const bool in = affine_below(W, m.x, m.y, m.z, m.w, thr2);
+            const double d0 = m.z - mu0, d1 = m.w - mu1, d2 = m.x - mu2, d3 = m.y - mu3;
+            c00 += in ? d0 * d0 : 0.0; c01 += in ? d0 * d1 : 0.0; c02 += in ? d0 * d2 : 0.0; c03 += in ? d0 * d3 : 0.0;
+            c11 += in ? d1 * d1 : 0.0; c12 += in ? d1 * d2 : 0.0; c13 += in ? d1 * d3 : 0.0;
+            c22 += in ? d2 * d2 : 0.0; c23 += in ? d2 * d3 : 0.0; c33 += in ? d3 * d3 : 0.0;
+        }
+        red[0 * 256 + tid] = c00; red[1 * 256 + tid] = c01; red[2 * 256 + tid] = c02; red[3 * 256 + tid] = c03;
+        red[4 * 256 + tid] = c11; red[5 * 256 + tid] = c12; red[6 * 256 + tid] = c13;
+        red[7 * 256 + tid] = c22; red[8 * 256 + tid] = c23; red[9 * 256 + tid] = c33;
+        tree_sum<10>(red, tid);
+        // every thread runs the same Jacobi on the same totals
+        double C[4][4], V[4][4], w[4];
+        C[0][0] = red[0]; C[0][1] = C[1][0] = red[256]; C[0][2] = C[2][0] = red[512]; C[0][3] = C[3][0] = red[768];
+        C[1][1] = red[1024]; C[1][2] = C[2][1] = red[1280]; C[1][3] = C[3][1] = red[1536];
+        C[2][2] = red[1792]; C[2][3] = C[3][2] = red[2048]; C[3][3] = red[2304];
+        eig4_fixed(C, V, w);
+        int m = 0;
+        if (w[1] < w[m]) m = 1;
+        if (w[2] < w[m]) m = 2;
+        if (w[3] < w[m]) m = 3;
+        AffineHyp R;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) R.v[q] = m == 0 ? V[q][0] : m == 1 ? V[q][1] : m == 2 ? V[q][2] : V[q][3];
+        R.v[4] = -(((R.v[0] * mu0 + R.v[1] * mu1) + R.v[2] * mu2) + R.v[3] * mu3);
+        affine_bounds(R, thr_lo, thr_hi);
+        // all matches counted again under the refit; it replaces the winner when it holds at least as many
+        int mine = 0;
+        for (int i = tid; i < k; i += 256) {
+            const double4 mm = load_match(job, i);
+            mine += affine_below(R, mm.x, mm.y, mm.z, mm.w, thr2) ? 1 : 0;
+        }
+        if (mine) atomicAdd(&s_n, mine);
+        __syncthreads();
+        ran = 1;
+        if (s_n >= win_count) { accepted = 1; W = R; }
+    }
+    if (tid == 0) {
+        if (job.F_out) {
+            for (int i = 0; i < 9; ++i) job.F_out[i] = 0.0;
+            job.F_out[2] = W.v[0]; job.F_out[5] = W.v[1]; job.F_out[6] = W.v[2]; job.F_out[7] = W.v[3]; job.F_out[8] = W.v[4];
+        }
+        if (results) results[jid] = osfm_ransac_affine_result{win_iter, win_count, ran, accepted};
+    }
+    // ordered list of the inlier ids under the final F_A
+    for (int c0 = 0; c0 < k; c0 += 256) {
+        const int i = c0 + tid;
+        bool in = false;
+        if (i < k) {
+            const double4 m = load_match(job, i);
+            in = affine_below(W, m.x, m.y, m.z, m.w, thr2);
+        }
+        const unsigned long long bal = __ballot(in);
+        if (lane == 0) s_wave[wave] = __popcll(bal);
+        __syncthreads();
+        int off = s_run;
+        for (int wv = 0; wv < wave; ++wv) off += s_wave[wv];
+        if (in) job.inliers_out[off + __popcll(bal & ((1ull << lane) - 1ull))] = i;
+        __syncthreads();
+        if (tid == 0) s_run += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        __syncthreads();
+    }
+    if (tid == 0) *job.count_out = s_run;
+}
+
+size_t affine_scratch_bytes(int num_jobs)
+{
+    return (size_t)std::max(num_jobs, 1) * (kRansacSplit * sizeof(AffineSlot) + 16);
+}
+
+void launch_ransac_affine(const RansacJob *d_jobs, int num_jobs, int max_iterations, double threshold, int refit,
+    uint64_t seed, void *scratch, osfm_ransac_affine_result *d_results, hipStream_t s)
+{
+    if (num_jobs <= 0) return;
+    AffineSlot *slots = static_cast<AffineSlot *>(scratch);
+    int32_t *done = reinterpret_cast<int32_t *>(static_cast<char *>(scratch) + (size_t)num_jobs * kRansacSplit * sizeof(AffineSlot));
+    (void)hipMemsetAsync(done, 0, (size_t)num_jobs * sizeof(int32_t), s);
+    hipLaunchKernelGGL(ransac_affine_kernel, dim3(num_jobs * kRansacSplit), dim3(256), 0, s, d_jobs, num_jobs, max_iterations,
+        threshold * threshold, refit != 0 ? 1 : 0, seed, slots, done, d_results);
+}
+
+}  // namespace osfm

@@ -55,9 +55,9 @@ class HipExhaustiveMatching:
         self._h = C.c_void_p()
         if isinstance(device, (list, tuple, np.ndarray)):
             ids = (C.c_int * len(device))(*[int(d) for d in device])
-            capi.check(capi.lib.osfm_match_create_multi(ids, len(device), num_views, C.byref(self.opts), C.byref(self._h)))
+            capi.check(capi.lib.osfm_match_create_multi_v2(ids, len(device), num_views, C.byref(self.opts), C.byref(self._h)))
         else:
-            capi.check(capi.lib.osfm_match_create(int(device), num_views, C.byref(self.opts), C.byref(self._h)))
+            capi.check(capi.lib.osfm_match_create_v2(int(device), num_views, C.byref(self.opts), C.byref(self._h)))
         self.num_views = num_views
 
     def devices(self):
@@ -261,6 +261,28 @@ class HipExhaustiveMatching:
             capi._ptr(corr, C.c_int32), corr.shape[0], C.byref(o), C.c_uint64(pair_id),
             capi._ptr(inl, C.c_int32), C.byref(n), capi._ptr(F, C.c_double)))
         return n.value, inl[:max(n.value, 0)].copy(), F.reshape(3, 3)
+
+    @staticmethod
+    def ransac_affine(pos1, pos2, corr, max_iterations=1000, threshold=0.0015, seed=0, pair_id=0, refit=True, device=0):
+        """osfm_ransac_affine for one pair of orthographic views; returns (count, inlier ids, F, record): the number of
+        inliers (-1 below 4 matches), their ascending indices into corr, the affine fundamental matrix in the 3x3 layout
+        of ransac_fundamental's F, and a dict of the result record (best_iteration, ransac_inliers, refit_ran,
+        refit_accepted)."""
+        pos1 = np.ascontiguousarray(pos1, dtype=np.float32).reshape(-1, 2)
+        pos2 = np.ascontiguousarray(pos2, dtype=np.float32).reshape(-1, 2)
+        corr = np.ascontiguousarray(corr, dtype=np.int32).reshape(-1, 2)
+        o = capi.RansacAffineOptions(max_iterations, 1 if refit else 0, threshold, seed)
+        inl = np.zeros(max(corr.shape[0], 1), dtype=np.int32)
+        n = C.c_int32()
+        F = np.zeros(9)
+        r = capi.RansacAffineResult(-1, 0, 0, 0)
+        capi.check(capi.lib.osfm_ransac_affine(
+            device, capi._ptr(pos1, C.c_float), pos1.shape[0], capi._ptr(pos2, C.c_float), pos2.shape[0],
+            capi._ptr(corr, C.c_int32), corr.shape[0], C.byref(o), C.c_uint64(pair_id),
+            capi._ptr(inl, C.c_int32), C.byref(n), capi._ptr(F, C.c_double), C.byref(r)))
+        rec = {"best_iteration": r.best_iteration, "ransac_inliers": r.ransac_inliers,
+               "refit_ran": r.refit_ran, "refit_accepted": r.refit_accepted}
+        return n.value, inl[:max(n.value, 0)].copy(), F.reshape(3, 3), rec
 
     def use_result_buffer(self, buf):
         """Lets the caller provide the (rows, 2) int32 array compute() writes the match

@@ -380,6 +380,7 @@ class Result:
     captured: dict = field(default_factory=dict)
     pair_status: np.ndarray | None = None
     initial_alignments: list = field(default_factory=list)      # one tk.Alignment per group (initial_alignment="tk")
+    verification: str = "none"       # model of the geometric verification: "none", "fundamental" or "affine"
 
 
 def _problem(model, cams, const, width, height, points, xy, obs_cam, obs_pt):
@@ -425,7 +426,8 @@ _list_buffers = _ListBufferPool()
 
 
 def match_and_build_tracks(iset, matcher="exhaustive", device=0, verify=True, timings=None, pairs=None):
-    """calculateTracksUsingMVE up to (and including) the track conversion."""
+    """calculateTracksUsingMVE up to (and including) the track conversion.  verify: True -- RANSAC-F as the reference;
+    "affine" -- the affine RANSAC for orthographic views; False -- none.  info["verification"] names the model used."""
     W, H = iset.width, iset.height
 
     def upload(m, v):
@@ -450,7 +452,7 @@ def tracks_from_images(images, matcher="exhaustive", device=0, verify=True, down
     from there into the matcher without the descriptors' way through the host; then matching, RANSAC-F, the tracks
     and the reference's pixel conversion, import_width * (pos + 0.5) on BOTH axes with pos normalised by the size of
     the feature image (matching_mve.cpp:455-466; import_width is the last view's, as the reference's imageWidth is
-    whichever view wrote it last).  options: the capi.MatchOptions to start from (geometric_verification and the
+    whichever view wrote it last).  verify: as match_and_build_tracks.  options: the capi.MatchOptions to start from (geometric_verification and the
     matcher type are set here).  Returns (TrackTable, track colours (num_tracks, 3) uint8, info).
 
     masks: one uint8 mask [mh, mw] or None per image, the reference's --mask-folder (reconstruct.cpp:47-53).  With
@@ -533,7 +535,13 @@ def _match_and_build(V, upload, sizes, image_width, matcher, device, verify, tim
         o = capi.MatchOptions.from_buffer_copy(options)
     else:
         o = capi.default_match_options()
+    # verify: False -- no geometric verification; True -- the reference's RANSAC-F; "affine" -- the affine
+    # fundamental matrix of two orthographic views (osfm_ransac_affine)
+    if isinstance(verify, str) and verify != "affine":
+        raise ValueError(f"verify: True, False or \"affine\", not {verify!r}")
     o.geometric_verification = 1 if verify else 0
+    if verify == "affine":
+        o.ransac_model = capi.RANSAC_AFFINE
     cls = HipExhaustiveMatching if matcher == "exhaustive" else HipCascadeHashing
     import queue
     import threading
@@ -678,7 +686,9 @@ def _match_and_build(V, upload, sizes, image_width, matcher, device, verify, tim
     tm.convert_s = time.perf_counter() - t0
     info = {"num_pairs": int(pf.shape[0]), "matched_pairs": int(builder.num_pairs), "correspondences": int(builder.num_matches),
             "num_mve_tracks": int(summary.num_tracks), "invalid_mve_tracks": int(summary.num_invalid_tracks),
-            "pair_status": status}
+            "pair_status": status,
+            "verification": "none" if not o.geometric_verification else
+                            "affine" if o.ransac_model == capi.RANSAC_AFFINE else "fundamental"}
     try:
         st = m.stats()
         info["match_stats"] = {f[0]: getattr(st, f[0]) for f in st._fields_ if not f[0].startswith("reserved")}
@@ -1072,7 +1082,7 @@ def reconstruct(iset, solver=0, matcher="exhaustive", device=0, verify=True, rot
     track building, group ordering and the incremental pose estimation.
     solver 0: quaternion cameras (ORTHO_QUATERNION); 1..3: Euler cameras with that many
     free angle blocks (3 = ORTHO_EULER_ALL_DOF: phi, theta, roll and the offsets).
-    local_solver: run_pose_estimation's."""
+    verify: match_and_build_tracks' (True, False or "affine").  local_solver: run_pose_estimation's."""
     tm = Timings()
     t_all = time.perf_counter()
     tt, info = match_and_build_tracks(iset, matcher, device, verify, tm)
