@@ -3,20 +3,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include <vector>
 
 #include "../../include/osfm_hip.h"
 
 namespace osfm {
 
-// The last extraction of a context as the hand-off reads it.  Everything is in generation order; row i of
-// FeatureSet's view is generation row order[i], whose descriptor is row (rows ? rows[order[i]] : order[i]) of desc.
-struct DeviceFeatures {
-    const float *desc = nullptr;                    // device: [.][128] (SIFT) or [.][64] (SURF)
-    int n = 0;
-    const std::vector<float> *positions = nullptr, *scale = nullptr, *orientation = nullptr;
-    const std::vector<int32_t> *order = nullptr, *rows = nullptr;
-};
+struct DetectorContext;
 
 // osfm_sift_extract / osfm_surf_extract on d_pixels (width x height x channels bytes on the context's device),
 // which the context's stream reads once `image_ready` has happened.  Same errors; colours and normalised
@@ -25,7 +17,9 @@ int sift_extract_device(osfm_sift *ctx, const uint8_t *d_pixels, hipEvent_t imag
     osfm_sift_summary *summary);
 int surf_extract_device(osfm_surf *ctx, const uint8_t *d_pixels, hipEvent_t image_ready, int width, int height, int channels,
     osfm_surf_summary *summary);
-int sift_device_features(osfm_sift *ctx, DeviceFeatures *out);
-int surf_device_features(osfm_surf *ctx, DeviceFeatures *out);
+// The context's shared part (detector_context.h), where the last extraction lies: desc and n_desc on the device, the
+// per-row arrays in generation order on the host.
+const DetectorContext *detector_of(const osfm_sift *ctx);
+const DetectorContext *detector_of(const osfm_surf *ctx);
 
 }  // namespace osfm

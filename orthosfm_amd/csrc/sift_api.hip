@@ -1,13 +1,13 @@
 // C ABI of the SIFT extraction (include/osfm_hip.h, "SIFT feature extraction"): owns the pyramid, runs the
 // stages of sift_kernels.hip in the reference's order, and keeps FeatureSet::compute_sift's view of the result.
+// What an extraction shares with SURF's is detector_context.h's.
 #include <cmath>
 #include <cstring>
 #include <memory>
 #include <numeric>
 
+#include "detector_context.h"
 #include "feature_device.h"
-#include "feature_view.h"
-#include "osfm_common.h"
 #include "sift_kernels.h"
 
 using namespace osfm;
@@ -52,28 +52,12 @@ void plan_octave(const osfm_sift_options &o, float has_sigma, OctavePlan *p)
 
 }  // namespace
 
-struct osfm_sift {
-    int device = 0, max_w = 0, max_h = 0;
+struct osfm_sift : DetectorContext {
     osfm_sift_options opts{};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {};
     std::vector<OctavePlan> plan;          // blur weights per octave
-    DeviceBuffer pixels, pyramid, cand, moved, kps, keep, counts, total, sigma, num_ori, oris, jobs, desc;
+    DeviceBuffer pyramid, sigma, num_ori, oris, jobs;
     size_t pyramid_floats = 0;
-    int max_blocks = 0;
-    // the last extraction
-    bool have = false;
-    PyramidView view{};
-    int n_cand = 0, n_kp = 0, n_desc = 0;
-    std::vector<Keypoint> h_kps;
-    std::vector<float> positions, scale, orientation, normalized;   // in generation order
-    std::vector<uint8_t> colors;
-    std::vector<int32_t> order;            // FeatureSet's order: row i is generation row order[i]
-    ~osfm_sift()
-    {
-        for (auto &e : ev) event_destroy(e);
-        stream_destroy(stream);
-    }
+    PyramidView view{};                    // of the last extraction
 };
 
 namespace {
@@ -167,11 +151,7 @@ int extract(osfm_sift *c, const uint8_t *pixels, const uint8_t *d_pixels, hipEve
 
     // ---- scale space
     OSFM_HIP_CHECK(hipEventRecord(c->ev[0], s));
-    const size_t bytes = (size_t)width * height * channels;
-    if (pixels) {
-        OSFM_HIP_CHECK(hipMemcpyAsync(c->pixels.ptr, pixels, bytes, hipMemcpyHostToDevice, s));
-        d_pixels = c->pixels.as<uint8_t>();
-    } else if (image_ready) OSFM_HIP_CHECK(hipStreamWaitEvent(s, image_ready, 0));
+    OSFM_RETURN_IF(stage_image(c, pixels, (size_t)width * height * channels, image_ready, &d_pixels));
     launch_to_float(s, d_pixels, width, height, channels, orig);
     const float hs = 0.866025403784439f;       // rescale_half_size_gaussian's default sigma
     const float hw1 = std::exp(-0.5f / (2.0f * (hs * hs))), hw2 = std::exp(-2.5f / (2.0f * (hs * hs))),
@@ -211,49 +191,28 @@ int extract(osfm_sift *c, const uint8_t *pixels, const uint8_t *d_pixels, hipEve
 
     // ---- extrema: count per workgroup, scan, write in (octave, sample, y, x) order
     OSFM_HIP_CHECK(hipEventRecord(c->ev[1], s));
-    int32_t *counts = c->counts.as<int32_t>(), *total = c->total.as<int32_t>();
     Keypoint *cand = c->cand.as<Keypoint>();
-    for (int pass = 0; pass < 2; ++pass) {
-        int base = 0;
-        for (int oi = 0; oi < pv.num_octaves; ++oi) {
-            const OctaveView &ov = pv.oct[oi];
-            const size_t plane = (size_t)ov.w * ov.h;
-            for (int si = 0; si < S; ++si) {
-                const float *d0 = ov.dog + (size_t)si * plane;
-                launch_extrema(s, d0, d0 + plane, d0 + 2 * plane, ov.w, ov.h, base, counts, pass ? counts : nullptr, cand,
-                    o.max_keypoints, (float)(oi + o.min_octave), (float)si);
-                base += extrema_blocks(ov.w, ov.h);
-            }
-        }
-        if (!pass) launch_scan(s, counts, base, total);
-    }
-    int32_t n_cand = 0;
-    OSFM_HIP_CHECK(hipMemcpyAsync(&n_cand, total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    OSFM_HIP_CHECK(hipStreamSynchronize(s));
-    if (n_cand > o.max_keypoints) {
-        set_error("osfm_sift_extract: %d candidates exceed max_keypoints %d", n_cand, o.max_keypoints);
-        return OSFM_E_CAPACITY;
-    }
+    OSFM_RETURN_IF(find_candidates(c, "osfm_sift_extract", pv.num_octaves, 0, S, [&](int oi, int si, int base, const int32_t *offsets) {
+        const OctaveView &ov = pv.oct[oi];
+        const size_t plane = (size_t)ov.w * ov.h;
+        const float *d0 = ov.dog + (size_t)si * plane;
+        launch_extrema(s, d0, d0 + plane, d0 + 2 * plane, ov.w, ov.h, base, c->counts.as<int32_t>(), offsets, cand, o.max_keypoints,
+            (float)(oi + o.min_octave), (float)si);
+        return extrema_blocks(ov.w, ov.h);
+    }));
+    const int n_cand = c->n_cand;
 
     // ---- localisation, compaction, and sigma / scale from the C library's powf on the host
     OSFM_HIP_CHECK(hipEventRecord(c->ev[2], s));
-    int32_t n_kp = 0;
     std::vector<Keypoint> h_kps;
     if (n_cand > 0) {
         LocaliseParams prm;
         prm.contrast_threshold = o.contrast_threshold;
         prm.score_threshold = ((o.edge_ratio_threshold + 1.0f) * (o.edge_ratio_threshold + 1.0f)) / o.edge_ratio_threshold;
-        launch_localise(s, pv, prm, cand, n_cand, c->moved.as<Keypoint>(), c->keep.as<uint8_t>(), counts);
-        launch_scan(s, counts, (n_cand + kBlock - 1) / kBlock, total);
-        launch_compact(s, c->moved.as<Keypoint>(), c->keep.as<uint8_t>(), counts, n_cand, c->kps.as<Keypoint>());
-        OSFM_HIP_CHECK(hipMemcpyAsync(&n_kp, total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        OSFM_HIP_CHECK(hipStreamSynchronize(s));
-        h_kps.resize((size_t)n_kp);
-        if (n_kp) {
-            OSFM_HIP_CHECK(hipMemcpyAsync(h_kps.data(), c->kps.ptr, (size_t)n_kp * sizeof(Keypoint), hipMemcpyDeviceToHost, s));
-            OSFM_HIP_CHECK(hipStreamSynchronize(s));
-        }
+        launch_localise(s, pv, prm, cand, n_cand, c->moved.as<Keypoint>(), c->keep.as<uint8_t>(), c->counts.as<int32_t>());
     }
+    OSFM_RETURN_IF(compact_keypoints(c, &h_kps));
+    const int n_kp = c->n_kp;
     std::vector<float> sigma((size_t)n_kp), abs_scale((size_t)n_kp);
     for (int i = 0; i < n_kp; ++i) {
         const Keypoint &k = h_kps[(size_t)i];
@@ -297,44 +256,23 @@ int extract(osfm_sift *c, const uint8_t *pixels, const uint8_t *d_pixels, hipEve
     std::memset(&sum, 0, sizeof(sum));
     sum.num_candidates = n_cand; sum.num_keypoints = n_kp; sum.num_descriptors = n_desc; sum.num_octaves = pv.num_octaves;
     for (const Keypoint &k : h_kps) sum.keypoints_per_octave[(int)k.octave - o.min_octave]++;
-    c->positions.resize((size_t)n_desc * 2); c->normalized.resize((size_t)n_desc * 2);
-    c->scale.resize((size_t)n_desc); c->orientation.resize((size_t)n_desc); c->colors.resize((size_t)n_desc * 3);
+    begin_rows(c, n_desc);
     for (int j = 0; j < n_desc; ++j) {
         const Keypoint &k = h_kps[(size_t)jobs[(size_t)j].keypoint];
         sum.descriptors_per_octave[(int)k.octave - o.min_octave]++;
         const float factor = (float)std::pow(2.0, (double)(int)k.octave);
-        const float x = factor * (k.x + 0.5f) - 0.5f, y = factor * (k.y + 0.5f) - 0.5f;
-        c->positions[2 * (size_t)j] = x; c->positions[2 * (size_t)j + 1] = y;
+        c->positions[2 * (size_t)j] = factor * (k.x + 0.5f) - 0.5f;
+        c->positions[2 * (size_t)j + 1] = factor * (k.y + 0.5f) - 0.5f;
         c->scale[(size_t)j] = abs_scale[(size_t)jobs[(size_t)j].keypoint];
         c->orientation[(size_t)j] = jobs[(size_t)j].orientation;
-        if (pixels) feature_view_row(pixels, width, height, channels, x, y, &c->colors[3 * (size_t)j], &c->normalized[2 * (size_t)j]);
     }
-    feature_view_order(c->scale, &c->order);
     float ms[5] = {};
-    for (int i = 0; i < 5; ++i) OSFM_HIP_CHECK(hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
+    OSFM_RETURN_IF(finish_rows(c, pixels, width, height, channels, ms, &sum.total_ms));
     sum.scale_space_ms = ms[0]; sum.extrema_ms = ms[1]; sum.localisation_ms = ms[2]; sum.orientation_ms = ms[3];
     sum.descriptor_ms = ms[4];
-    sum.total_ms = (double)ms[0] + ms[1] + ms[2] + ms[3] + ms[4];
     c->view = pv;
-    c->n_cand = n_cand; c->n_kp = n_kp; c->n_desc = n_desc;
-    c->h_kps.swap(h_kps);
     c->have = true;
     if (sum_out) *sum_out = sum;
-    return OSFM_OK;
-}
-
-// What osfm_sift_extract checks before it runs
-int check_image(osfm_sift *c, int width, int height, int channels)
-{
-    if (channels != 1 && channels != 3) {
-        set_error("osfm_sift_extract: %d channels: a grey (1) or colour (3) image is expected", channels);
-        return OSFM_E_ARG;
-    }
-    if (width < 1 || height < 1) { set_error("osfm_sift_extract: image size %d x %d", width, height); return OSFM_E_ARG; }
-    if (width > c->max_w || height > c->max_h) {
-        set_error("osfm_sift_extract: a %d x %d image exceeds the context's %d x %d", width, height, c->max_w, c->max_h);
-        return OSFM_E_RANGE;
-    }
     return OSFM_OK;
 }
 
@@ -345,24 +283,11 @@ namespace osfm {
 int sift_extract_device(osfm_sift *c, const uint8_t *d_pixels, hipEvent_t image_ready, int width, int height, int channels,
     osfm_sift_summary *summary)
 {
-    if (!c || !d_pixels) { set_error("osfm_sift_extract: null argument"); return OSFM_E_ARG; }
-    c->have = false;
-    OSFM_RETURN_IF(check_image(c, width, height, channels));
-    OSFM_HIP_CHECK(hipSetDevice(c->device));
-    const int rc = extract(c, nullptr, d_pixels, image_ready, width, height, channels, summary);
-    if (rc != OSFM_OK) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return run_extract(c, "osfm_sift_extract", d_pixels, width, height, channels,
+        [&] { return extract(c, nullptr, d_pixels, image_ready, width, height, channels, summary); });
 }
 
-int sift_device_features(osfm_sift *c, DeviceFeatures *out)
-{
-    if (!c || !out) { set_error("osfm_sift: null argument"); return OSFM_E_ARG; }
-    if (!c->have) { set_error("osfm_sift: no extraction"); return OSFM_E_STATE; }
-    out->desc = c->desc.as<float>(); out->n = c->n_desc;
-    out->positions = &c->positions; out->scale = &c->scale; out->orientation = &c->orientation;
-    out->order = &c->order; out->rows = nullptr;
-    return OSFM_OK;
-}
+const DetectorContext *detector_of(const osfm_sift *c) { return c; }
 
 }  // namespace osfm
 
@@ -390,10 +315,7 @@ int osfm_sift_create(int device, int max_width, int max_height, const osfm_sift_
     (void)osfm_sift_options_default(&o);
     if (opts) o = *opts;
     const int S = o.num_samples_per_octave;
-    if (max_width < 1 || max_height < 1 || max_width > 16384 || max_height > 16384) {
-        set_error("osfm_sift_create: image size %d x %d outside 1..16384", max_width, max_height);
-        return OSFM_E_ARG;
-    }
+    OSFM_RETURN_IF(check_bounds("osfm_sift_create", max_width, max_height));
     if (o.min_octave > 0) {
         set_error("osfm_sift_create: min_octave %d: the first octave is the image (0) or the doubled image (-1)", o.min_octave);
         return OSFM_E_ARG;
@@ -408,12 +330,9 @@ int osfm_sift_create(int device, int max_width, int max_height, const osfm_sift_
     }
     // Sift::Sift: a negative contrast threshold means the default
     if (o.contrast_threshold < 0.0f) o.contrast_threshold = 0.02f / (float)S;
-    int ndev = 0;
-    OSFM_HIP_CHECK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) { set_error("osfm_sift_create: device %d of %d", device, ndev); return OSFM_E_ARG; }
-    OSFM_HIP_CHECK(hipSetDevice(device));
+    OSFM_RETURN_IF(select_device("osfm_sift_create", device));
     std::unique_ptr<osfm_sift> c(new osfm_sift);
-    c->device = device; c->max_w = max_width; c->max_h = max_height; c->opts = o;
+    c->opts = o;
     // the blur of every octave: the doubled image has twice the inherent blur, octave 0 the inherent blur, every
     // later octave the base blur
     for (int i = o.min_octave; i <= o.max_octave; ++i) {
@@ -431,73 +350,33 @@ int osfm_sift_create(int device, int max_width, int max_height, const osfm_sift_
     }
     std::vector<std::pair<int, int>> sizes;
     (void)octave_sizes(o, max_width, max_height, &sizes);
-    for (auto &z : sizes) c->max_blocks += S * extrema_blocks(z.first, z.second);
-    c->max_blocks = std::max(c->max_blocks, (o.max_keypoints + kBlock - 1) / kBlock) + 1;
+    int blocks = 0;
+    for (auto &z : sizes) blocks += S * extrema_blocks(z.first, z.second);
+    OSFM_RETURN_IF(init_detector(c.get(), device, max_width, max_height, o.max_keypoints, blocks, 6));
     c->pyramid_floats = pyramid_size(o, max_width, max_height);
     const size_t K = (size_t)o.max_keypoints;
-    OSFM_RETURN_IF(c->pixels.reserve((size_t)max_width * max_height * 3));
     OSFM_RETURN_IF(c->pyramid.reserve(c->pyramid_floats * sizeof(float)));
-    OSFM_RETURN_IF(c->cand.reserve(K * sizeof(Keypoint)));
-    OSFM_RETURN_IF(c->moved.reserve(K * sizeof(Keypoint)));
-    OSFM_RETURN_IF(c->kps.reserve(K * sizeof(Keypoint)));
-    OSFM_RETURN_IF(c->keep.reserve(K));
-    OSFM_RETURN_IF(c->counts.reserve((size_t)c->max_blocks * sizeof(int32_t)));
-    OSFM_RETURN_IF(c->total.reserve(sizeof(int32_t)));
     OSFM_RETURN_IF(c->sigma.reserve(K * sizeof(float)));
     OSFM_RETURN_IF(c->num_ori.reserve(K * sizeof(int32_t)));
     OSFM_RETURN_IF(c->oris.reserve(K * kMaxOrientations * sizeof(float)));
     OSFM_RETURN_IF(c->jobs.reserve(K * sizeof(DescriptorJob)));
     OSFM_RETURN_IF(c->desc.reserve(K * 128 * sizeof(float)));
-    OSFM_HIP_CHECK(stream_create(&c->stream));
-    for (auto &e : c->ev) OSFM_HIP_CHECK(event_create(&e, true));
     *out = c.release();
     return OSFM_OK;
 }
 
-int osfm_sift_destroy(osfm_sift *c)
-{
-    if (!c) return OSFM_OK;
-    (void)hipSetDevice(c->device);
-    delete c;
-    return OSFM_OK;
-}
+int osfm_sift_destroy(osfm_sift *c) { return destroy_context(c); }
 
 int osfm_sift_extract(osfm_sift *c, const uint8_t *pixels, int width, int height, int channels, osfm_sift_summary *summary)
 {
-    if (!c || !pixels) { set_error("osfm_sift_extract: null argument"); return OSFM_E_ARG; }
-    c->have = false;          // whatever comes of this call, the previous result is gone
-    OSFM_RETURN_IF(check_image(c, width, height, channels));
-    OSFM_HIP_CHECK(hipSetDevice(c->device));
-    const int rc = extract(c, pixels, nullptr, nullptr, width, height, channels, summary);
-    if (rc != OSFM_OK) (void)hipStreamSynchronize(c->stream);   // nothing of a failed call may still run
-    return rc;
+    return run_extract(c, "osfm_sift_extract", pixels, width, height, channels,
+        [&] { return extract(c, pixels, nullptr, nullptr, width, height, channels, summary); });
 }
 
 int osfm_sift_download(osfm_sift *c, float *descriptors, float *positions, float *scale, float *orientation, uint8_t *colors,
     float *normalized_positions)
 {
-    if (!c) { set_error("osfm_sift_download: null argument"); return OSFM_E_ARG; }
-    if (!c->have) { set_error("osfm_sift_download: no extraction to download"); return OSFM_E_STATE; }
-    OSFM_HIP_CHECK(hipSetDevice(c->device));
-    const size_t n = (size_t)c->n_desc;
-    if (descriptors && n) {
-        std::vector<float> gen(n * 128);
-        OSFM_HIP_CHECK(hipMemcpyAsync(gen.data(), c->desc.ptr, gen.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-        for (size_t i = 0; i < n; ++i) std::memcpy(descriptors + i * 128, gen.data() + (size_t)c->order[i] * 128, 128 * sizeof(float));
-    }
-    for (size_t i = 0; i < n; ++i) {
-        const size_t g = (size_t)c->order[i];
-        if (positions) { positions[2 * i] = c->positions[2 * g]; positions[2 * i + 1] = c->positions[2 * g + 1]; }
-        if (scale) scale[i] = c->scale[g];
-        if (orientation) orientation[i] = c->orientation[g];
-        if (colors) std::memcpy(colors + 3 * i, c->colors.data() + 3 * g, 3);
-        if (normalized_positions) {
-            normalized_positions[2 * i] = c->normalized[2 * g];
-            normalized_positions[2 * i + 1] = c->normalized[2 * g + 1];
-        }
-    }
-    return OSFM_OK;
+    return download_features(c, "osfm_sift_download", 128, descriptors, positions, scale, orientation, colors, normalized_positions);
 }
 
 int osfm_sift_debug_image(osfm_sift *c, int octave, int kind, int index, float *out, int32_t *width, int32_t *height)
@@ -519,16 +398,7 @@ int osfm_sift_debug_image(osfm_sift *c, int octave, int kind, int index, float *
 
 int osfm_sift_debug_keypoints(osfm_sift *c, int after_localisation, float *out, int32_t *count)
 {
-    if (!c) { set_error("osfm_sift_debug_keypoints: null argument"); return OSFM_E_ARG; }
-    if (!c->have) { set_error("osfm_sift_debug_keypoints: no extraction"); return OSFM_E_STATE; }
-    const int n = after_localisation ? c->n_kp : c->n_cand;
-    if (count) *count = n;
-    if (!out || !n) return OSFM_OK;
-    OSFM_HIP_CHECK(hipSetDevice(c->device));
-    OSFM_HIP_CHECK(hipMemcpyAsync(out, after_localisation ? c->kps.ptr : c->cand.ptr, (size_t)n * sizeof(Keypoint),
-        hipMemcpyDeviceToHost, c->stream));
-    OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OSFM_OK;
+    return debug_keypoints(c, "osfm_sift_debug_keypoints", after_localisation, out, count);
 }
 
 }  // extern "C"

@@ -5,14 +5,18 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
+#include "detect_kernels.h"
+
 namespace osfm {
 namespace sift {
+
+using detect::kBlock;
+using detect::Keypoint;
 
 constexpr int kMaxRadius = 32;      // largest blur radius ceil(sigma * 2.884) a context accepts
 constexpr int kMaxOctaves = 16;
 constexpr int kMaxImages = 16;      // S + 3 images per octave
 constexpr int kMaxOrientations = 18;  // strict local maxima of 36 circular bins
-constexpr int kBlock = 256;         // threads per workgroup of the per-pixel and per-candidate kernels
 
 struct BlurWeights {
     int ks;
@@ -28,10 +32,6 @@ struct OctaveView {
 struct PyramidView {
     int num_octaves, S, min_octave;
     OctaveView oct[kMaxOctaves];
-};
-
-struct Keypoint {    // Sift::Keypoint with the octave as a float: 16 bytes
-    float octave, sample, x, y;
 };
 
 struct LocaliseParams {
@@ -53,33 +53,12 @@ void launch_blur(hipStream_t s, const float *in, float *sep, float *out, const f
 // with offsets given the extrema are written at offsets[block_base + b] + rank, rows below `capacity` only.
 void launch_extrema(hipStream_t s, const float *d0, const float *d1, const float *d2, int w, int h, int block_base,
     int32_t *counts, const int32_t *offsets, Keypoint *out, int capacity, float octave, float sample);
-// exclusive scan of counts[n] in place; *total receives the sum
-void launch_scan(hipStream_t s, int32_t *counts, int n, int32_t *total);
 void launch_localise(hipStream_t s, PyramidView pyr, LocaliseParams prm, const Keypoint *cand, int n, Keypoint *out,
     uint8_t *keep, int32_t *counts);
-void launch_compact(hipStream_t s, const Keypoint *in, const uint8_t *keep, const int32_t *offsets, int n, Keypoint *out);
 void launch_orientation(hipStream_t s, PyramidView pyr, const Keypoint *kps, const float *sigma, int n, int32_t *num,
     float *orientations);
 void launch_descriptor(hipStream_t s, PyramidView pyr, const Keypoint *kps, const float *sigma, const DescriptorJob *jobs,
     int n, float *out);
-
-// Rank of this thread among the flagged threads of its workgroup (kBlock threads), in thread order, and their
-// number: the ranked write of the count / scan / write scheme, shared with the SURF kernels.
-__device__ inline int block_rank(bool flag, int *block_total)
-{
-    __shared__ int wave_count[kBlock / 64];
-    const unsigned long long m = __ballot(flag);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wave_count[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int i = 0; i < kBlock / 64; ++i) {
-        if (i < wave) before += wave_count[i];
-        total += wave_count[i];
-    }
-    *block_total = total;
-    return before + __popcll(m & ((1ull << lane) - 1ull));
-}
 
 inline int extrema_blocks(int w, int h)
 {

@@ -11,6 +11,8 @@
 namespace osfm {
 namespace sift {
 
+using detect::block_rank;
+
 namespace {
 
 constexpr double kPi = 3.14159265358979323846264338327950288;
@@ -121,7 +123,7 @@ __global__ __launch_bounds__(kBlock) void blur_cols_kernel(const float *in, floa
     }
 }
 
-// ----------------------------------------------------------------------------- ordered compaction
+// ----------------------------------------------------------------------------- extrema
 
 // Strict 26-neighbour extrema of the interior pixels, one thread per pixel in (y, x) order.
 template <bool WRITE>
@@ -161,31 +163,6 @@ __global__ __launch_bounds__(kBlock) void extrema_kernel(const float *d0, const 
         const int slot = offsets[block_base + blockIdx.x] + rank;
         if (slot < capacity) out[slot] = Keypoint{octave, sample, (float)x, (float)y};
     }
-}
-
-// Exclusive scan of counts[n] in place by one workgroup; *total = the sum.
-constexpr int kScanBlock = 1024;
-__global__ __launch_bounds__(kScanBlock) void scan_kernel(int32_t *counts, int n, int32_t *total)
-{
-    __shared__ int buf[kScanBlock];
-    int carry = 0;
-    for (int base = 0; base < n; base += kScanBlock) {
-        const int i = base + threadIdx.x;
-        const int v = i < n ? counts[i] : 0;
-        buf[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < kScanBlock; off <<= 1) {
-            const int t = (int)threadIdx.x >= off ? buf[threadIdx.x - off] : 0;
-            __syncthreads();
-            buf[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < n) counts[i] = carry + buf[threadIdx.x] - v;
-        const int chunk = buf[kScanBlock - 1];
-        __syncthreads();
-        carry += chunk;
-    }
-    if (threadIdx.x == 0) *total = carry;
 }
 
 // ----------------------------------------------------------------------------- localisation
@@ -274,16 +251,6 @@ __global__ __launch_bounds__(kBlock) void localise_kernel(PyramidView pyr, Local
     int total;
     (void)block_rank(ok, &total);
     if (threadIdx.x == 0) counts[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kBlock) void compact_kernel(const Keypoint *in, const uint8_t *keep, const int32_t *offsets, int n,
-    Keypoint *out)
-{
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    const bool flag = i < n && keep[i] != 0;
-    int total;
-    const int rank = block_rank(flag, &total);
-    if (flag) out[offsets[blockIdx.x] + rank] = in[i];   // at most n rows: `out` holds as many as `in`
 }
 
 // ----------------------------------------------------------------------------- orientation and descriptor
@@ -561,20 +528,10 @@ void launch_extrema(hipStream_t s, const float *d0, const float *d1, const float
             out, capacity, octave, sample);
 }
 
-void launch_scan(hipStream_t s, int32_t *counts, int n, int32_t *total)
-{
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kScanBlock), 0, s, counts, n, total);
-}
-
 void launch_localise(hipStream_t s, PyramidView pyr, LocaliseParams prm, const Keypoint *cand, int n, Keypoint *out,
     uint8_t *keep, int32_t *counts)
 {
     hipLaunchKernelGGL(localise_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pyr, prm, cand, n, out, keep, counts);
-}
-
-void launch_compact(hipStream_t s, const Keypoint *in, const uint8_t *keep, const int32_t *offsets, int n, Keypoint *out)
-{
-    hipLaunchKernelGGL(compact_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, in, keep, offsets, n, out);
 }
 
 void launch_orientation(hipStream_t s, PyramidView pyr, const Keypoint *kps, const float *sigma, int n, int32_t *num,

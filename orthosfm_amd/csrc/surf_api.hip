@@ -1,43 +1,26 @@
 // C ABI of the SURF extraction (include/osfm_hip.h, "SURF feature extraction"): owns the summed-area table and
 // the response maps, runs the stages of surf_kernels.hip in the reference's order, and keeps
-// FeatureSet::compute_surf's view of the result.
+// FeatureSet::compute_surf's view of the result.  What an extraction shares with SIFT's is detector_context.h's.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 
+#include "detector_context.h"
 #include "feature_device.h"
-#include "feature_view.h"
-#include "osfm_common.h"
 #include "surf_kernels.h"
 
 using namespace osfm;
 using namespace osfm::surf;
 
-struct osfm_surf {
-    int device = 0, max_w = 0, max_h = 0;
+struct osfm_surf : DetectorContext {
     osfm_surf_options opts{};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[7] = {};
-    DeviceBuffer pixels, sat, maps, cand, moved, kps, keep, counts, total, table, weights, ori_jobs, ori_out, desc_jobs, desc,
-        status;
+    DeviceBuffer sat, maps, table, weights, ori_jobs, ori_out, desc_jobs, status;
     size_t map_floats = 0;
-    int max_blocks = 0;
-    // the last extraction
-    bool have = false;
+    // the last extraction (rows: generation row j is descriptor job rows[j])
     int width = 0, height = 0;
     MapsView view{};
-    int n_cand = 0, n_kp = 0, n_desc = 0;
-    std::vector<int32_t> rows;             // generation row j is descriptor job rows[j]
-    std::vector<float> positions, scale, orientation, normalized;   // in generation order
-    std::vector<uint8_t> colors;
-    std::vector<int32_t> order;            // FeatureSet's order: row i is generation row order[i]
-    ~osfm_surf()
-    {
-        for (auto &e : ev) event_destroy(e);
-        stream_destroy(stream);
-    }
 };
 
 namespace {
@@ -100,10 +83,7 @@ int extract(osfm_surf *c, const uint8_t *pixels, const uint8_t *d_pixels, hipEve
 
     // ---- summed-area table
     OSFM_HIP_CHECK(hipEventRecord(c->ev[0], s));
-    if (pixels) {
-        OSFM_HIP_CHECK(hipMemcpyAsync(c->pixels.ptr, pixels, (size_t)width * height * channels, hipMemcpyHostToDevice, s));
-        d_pixels = c->pixels.as<uint8_t>();
-    } else if (image_ready) OSFM_HIP_CHECK(hipStreamWaitEvent(s, image_ready, 0));
+    OSFM_RETURN_IF(stage_image(c, pixels, (size_t)width * height * channels, image_ready, &d_pixels));
     launch_sat(s, d_pixels, width, height, channels, sat);
 
     // ---- response maps
@@ -121,46 +101,24 @@ int extract(osfm_surf *c, const uint8_t *pixels, const uint8_t *d_pixels, hipEve
 
     // ---- extrema: count per workgroup, scan, write in (octave, sample, y, x) order
     OSFM_HIP_CHECK(hipEventRecord(c->ev[2], s));
-    int32_t *counts = c->counts.as<int32_t>(), *total = c->total.as<int32_t>();
     Keypoint *cand = c->cand.as<Keypoint>();
-    for (int pass = 0; pass < 2; ++pass) {
-        int base = 0;
-        for (int oi = 0; oi < kOctaves; ++oi) {
-            const size_t plane = (size_t)mv.ow[oi] * mv.oh[oi];
-            for (int si = 1; si < 3; ++si) {
-                const float *m1 = mv.maps + mv.offset[oi] + (size_t)si * plane;
-                surf::launch_extrema(s, m1 - plane, m1, m1 + plane, mv.ow[oi], mv.oh[oi], base, counts, pass ? counts : nullptr, cand,
-                    o.max_keypoints, (float)oi, (float)si);
-                base += extrema_blocks(mv.ow[oi], mv.oh[oi]);
-            }
-        }
-        if (!pass) sift::launch_scan(s, counts, base, total);
-    }
-    int32_t n_cand = 0;
-    OSFM_HIP_CHECK(hipMemcpyAsync(&n_cand, total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    OSFM_HIP_CHECK(hipStreamSynchronize(s));
-    if (n_cand > o.max_keypoints) {
-        set_error("osfm_surf_extract: %d candidates exceed max_keypoints %d", n_cand, o.max_keypoints);
-        return OSFM_E_CAPACITY;
-    }
+    OSFM_RETURN_IF(find_candidates(c, "osfm_surf_extract", kOctaves, 1, 3, [&](int oi, int si, int base, const int32_t *offsets) {
+        const size_t plane = (size_t)mv.ow[oi] * mv.oh[oi];
+        const float *m1 = mv.maps + mv.offset[oi] + (size_t)si * plane;
+        launch_extrema(s, m1 - plane, m1, m1 + plane, mv.ow[oi], mv.oh[oi], base, c->counts.as<int32_t>(), offsets, cand,
+            o.max_keypoints, (float)oi, (float)si);
+        return extrema_blocks(mv.ow[oi], mv.oh[oi]);
+    }));
+    const int n_cand = c->n_cand;
 
     // ---- localisation and compaction
     OSFM_HIP_CHECK(hipEventRecord(c->ev[3], s));
-    int32_t n_kp = 0;
     std::vector<Keypoint> h_kps;
-    if (n_cand > 0) {
-        surf::launch_localise(s, mv, o.contrast_threshold, width, height, cand, n_cand, c->moved.as<Keypoint>(), c->keep.as<uint8_t>(),
-            counts);
-        sift::launch_scan(s, counts, (n_cand + kBlock - 1) / kBlock, total);
-        sift::launch_compact(s, c->moved.as<Keypoint>(), c->keep.as<uint8_t>(), counts, n_cand, c->kps.as<Keypoint>());
-        OSFM_HIP_CHECK(hipMemcpyAsync(&n_kp, total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        OSFM_HIP_CHECK(hipStreamSynchronize(s));
-        h_kps.resize((size_t)n_kp);
-        if (n_kp) {
-            OSFM_HIP_CHECK(hipMemcpyAsync(h_kps.data(), c->kps.ptr, (size_t)n_kp * sizeof(Keypoint), hipMemcpyDeviceToHost, s));
-            OSFM_HIP_CHECK(hipStreamSynchronize(s));
-        }
-    }
+    if (n_cand > 0)
+        launch_localise(s, mv, o.contrast_threshold, width, height, cand, n_cand, c->moved.as<Keypoint>(), c->keep.as<uint8_t>(),
+            c->counts.as<int32_t>());
+    OSFM_RETURN_IF(compact_keypoints(c, &h_kps));
+    const int n_kp = c->n_kp;
 
     // ---- orientation: the windows on the device, atan2 / sinf / cosf of the winner from the C library
     OSFM_HIP_CHECK(hipEventRecord(c->ev[4], s));
@@ -214,8 +172,7 @@ int extract(osfm_surf *c, const uint8_t *pixels, const uint8_t *d_pixels, hipEve
         if (status[j]) rows.push_back((int32_t)j);
     const int n_desc = (int)rows.size();     // <= n_kp <= n_cand <= max_keypoints: one per keypoint at most
     sum.num_descriptors = n_desc;
-    c->positions.resize((size_t)n_desc * 2); c->normalized.resize((size_t)n_desc * 2);
-    c->scale.resize((size_t)n_desc); c->orientation.resize((size_t)n_desc); c->colors.resize((size_t)n_desc * 3);
+    begin_rows(c, n_desc);
     for (int r = 0; r < n_desc; ++r) {
         const size_t j = (size_t)rows[(size_t)r];
         const Keypoint &k = h_kps[(size_t)job_kp[j]];
@@ -224,34 +181,15 @@ int extract(osfm_surf *c, const uint8_t *pixels, const uint8_t *d_pixels, hipEve
         c->positions[2 * (size_t)r] = k.x; c->positions[2 * (size_t)r + 1] = k.y;
         c->scale[(size_t)r] = kp_scale[(size_t)job_kp[j]];
         c->orientation[(size_t)r] = job_ori[j];
-        if (pixels) feature_view_row(pixels, width, height, channels, k.x, k.y, &c->colors[3 * (size_t)r], &c->normalized[2 * (size_t)r]);
     }
-    feature_view_order(c->scale, &c->order);
     float ms[6] = {};
-    for (int i = 0; i < 6; ++i) OSFM_HIP_CHECK(hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
+    OSFM_RETURN_IF(finish_rows(c, pixels, width, height, channels, ms, &sum.total_ms));
     sum.sat_ms = ms[0]; sum.response_ms = ms[1]; sum.extrema_ms = ms[2]; sum.localisation_ms = ms[3]; sum.orientation_ms = ms[4];
     sum.descriptor_ms = ms[5];
-    sum.total_ms = (double)ms[0] + ms[1] + ms[2] + ms[3] + ms[4] + ms[5];
     c->view = mv;
-    c->n_cand = n_cand; c->n_kp = n_kp; c->n_desc = n_desc;
     c->rows.swap(rows);
     c->have = true;
     if (sum_out) *sum_out = sum;
-    return OSFM_OK;
-}
-
-// What osfm_surf_extract checks before it runs
-int check_image(osfm_surf *c, int width, int height, int channels)
-{
-    if (channels != 1 && channels != 3) {
-        set_error("osfm_surf_extract: %d channels: a grey (1) or colour (3) image is expected", channels);
-        return OSFM_E_ARG;
-    }
-    if (width < 1 || height < 1) { set_error("osfm_surf_extract: image size %d x %d", width, height); return OSFM_E_ARG; }
-    if (width > c->max_w || height > c->max_h) {
-        set_error("osfm_surf_extract: a %d x %d image exceeds the context's %d x %d", width, height, c->max_w, c->max_h);
-        return OSFM_E_RANGE;
-    }
     return OSFM_OK;
 }
 
@@ -262,24 +200,11 @@ namespace osfm {
 int surf_extract_device(osfm_surf *c, const uint8_t *d_pixels, hipEvent_t image_ready, int width, int height, int channels,
     osfm_surf_summary *summary)
 {
-    if (!c || !d_pixels) { set_error("osfm_surf_extract: null argument"); return OSFM_E_ARG; }
-    c->have = false;
-    OSFM_RETURN_IF(check_image(c, width, height, channels));
-    OSFM_HIP_CHECK(hipSetDevice(c->device));
-    const int rc = extract(c, nullptr, d_pixels, image_ready, width, height, channels, summary);
-    if (rc != OSFM_OK) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return run_extract(c, "osfm_surf_extract", d_pixels, width, height, channels,
+        [&] { return extract(c, nullptr, d_pixels, image_ready, width, height, channels, summary); });
 }
 
-int surf_device_features(osfm_surf *c, DeviceFeatures *out)
-{
-    if (!c || !out) { set_error("osfm_surf: null argument"); return OSFM_E_ARG; }
-    if (!c->have) { set_error("osfm_surf: no extraction"); return OSFM_E_STATE; }
-    out->desc = c->desc.as<float>(); out->n = c->n_desc;
-    out->positions = &c->positions; out->scale = &c->scale; out->orientation = &c->orientation;
-    out->order = &c->order; out->rows = &c->rows;
-    return OSFM_OK;
-}
+const DetectorContext *detector_of(const osfm_surf *c) { return c; }
 
 }  // namespace osfm
 
@@ -301,29 +226,17 @@ int osfm_surf_create(int device, int max_width, int max_height, const osfm_surf_
     osfm_surf_options o;
     (void)osfm_surf_options_default(&o);
     if (opts) o = *opts;
-    if (max_width < 1 || max_height < 1 || max_width > 16384 || max_height > 16384) {
-        set_error("osfm_surf_create: image size %d x %d outside 1..16384", max_width, max_height);
-        return OSFM_E_ARG;
-    }
+    OSFM_RETURN_IF(check_bounds("osfm_surf_create", max_width, max_height));
     if (o.max_keypoints < 1) { set_error("osfm_surf_create: invalid options (max_keypoints >= 1)"); return OSFM_E_ARG; }
-    int ndev = 0;
-    OSFM_HIP_CHECK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) { set_error("osfm_surf_create: device %d of %d", device, ndev); return OSFM_E_ARG; }
-    OSFM_HIP_CHECK(hipSetDevice(device));
+    OSFM_RETURN_IF(select_device("osfm_surf_create", device));
     std::unique_ptr<osfm_surf> c(new osfm_surf);
-    c->device = device; c->max_w = max_width; c->max_h = max_height; c->opts = o;
-    c->map_floats = plan_maps(max_width, max_height, nullptr, &c->max_blocks);
+    c->opts = o;
+    int blocks = 0;
+    c->map_floats = plan_maps(max_width, max_height, nullptr, &blocks);
+    OSFM_RETURN_IF(init_detector(c.get(), device, max_width, max_height, o.max_keypoints, blocks, 7));
     const size_t K = (size_t)o.max_keypoints;
-    c->max_blocks = std::max(c->max_blocks, (int)((K + kBlock - 1) / kBlock)) + 1;
-    OSFM_RETURN_IF(c->pixels.reserve((size_t)max_width * max_height * 3));
     OSFM_RETURN_IF(c->sat.reserve((size_t)max_width * max_height * sizeof(Sat)));
     OSFM_RETURN_IF(c->maps.reserve(c->map_floats * sizeof(float)));
-    OSFM_RETURN_IF(c->cand.reserve(K * sizeof(Keypoint)));
-    OSFM_RETURN_IF(c->moved.reserve(K * sizeof(Keypoint)));
-    OSFM_RETURN_IF(c->kps.reserve(K * sizeof(Keypoint)));
-    OSFM_RETURN_IF(c->keep.reserve(K));
-    OSFM_RETURN_IF(c->counts.reserve((size_t)c->max_blocks * sizeof(int32_t)));
-    OSFM_RETURN_IF(c->total.reserve(sizeof(int32_t)));
     OSFM_RETURN_IF(c->table.reserve(sizeof(OriTable)));
     OSFM_RETURN_IF(c->weights.reserve(400 * sizeof(float)));
     OSFM_RETURN_IF(c->ori_jobs.reserve(K * sizeof(OriJob)));
@@ -332,8 +245,6 @@ int osfm_surf_create(int device, int max_width, int max_height, const osfm_surf_
     OSFM_RETURN_IF(c->desc_jobs.reserve((K + 1) * sizeof(DescJob)));
     OSFM_RETURN_IF(c->desc.reserve((K + 1) * 64 * sizeof(float)));
     OSFM_RETURN_IF(c->status.reserve((K + 1) * sizeof(int32_t)));
-    OSFM_HIP_CHECK(stream_create(&c->stream));
-    for (auto &e : c->ev) OSFM_HIP_CHECK(event_create(&e, true));
     // the orientation window's Gaussian (sigma 2.5) as the reference spells it: six significant digits
     OriTable table;
     int index = 0;
@@ -359,52 +270,18 @@ int osfm_surf_create(int device, int max_width, int max_height, const osfm_surf_
     return OSFM_OK;
 }
 
-int osfm_surf_destroy(osfm_surf *c)
-{
-    if (!c) return OSFM_OK;
-    (void)hipSetDevice(c->device);
-    delete c;
-    return OSFM_OK;
-}
+int osfm_surf_destroy(osfm_surf *c) { return destroy_context(c); }
 
 int osfm_surf_extract(osfm_surf *c, const uint8_t *pixels, int width, int height, int channels, osfm_surf_summary *summary)
 {
-    if (!c || !pixels) { set_error("osfm_surf_extract: null argument"); return OSFM_E_ARG; }
-    c->have = false;          // whatever comes of this call, the previous result is gone
-    OSFM_RETURN_IF(check_image(c, width, height, channels));
-    OSFM_HIP_CHECK(hipSetDevice(c->device));
-    const int rc = extract(c, pixels, nullptr, nullptr, width, height, channels, summary);
-    if (rc != OSFM_OK) (void)hipStreamSynchronize(c->stream);   // nothing of a failed call may still run
-    return rc;
+    return run_extract(c, "osfm_surf_extract", pixels, width, height, channels,
+        [&] { return extract(c, pixels, nullptr, nullptr, width, height, channels, summary); });
 }
 
 int osfm_surf_download(osfm_surf *c, float *descriptors, float *positions, float *scale, float *orientation, uint8_t *colors,
     float *normalized_positions)
 {
-    if (!c) { set_error("osfm_surf_download: null argument"); return OSFM_E_ARG; }
-    if (!c->have) { set_error("osfm_surf_download: no extraction to download"); return OSFM_E_STATE; }
-    OSFM_HIP_CHECK(hipSetDevice(c->device));
-    const size_t n = (size_t)c->n_desc;
-    if (descriptors && n) {
-        const size_t jobs = (size_t)c->rows.back() + 1;
-        std::vector<float> gen(jobs * 64);
-        OSFM_HIP_CHECK(hipMemcpyAsync(gen.data(), c->desc.ptr, gen.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-        for (size_t i = 0; i < n; ++i)
-            std::memcpy(descriptors + i * 64, gen.data() + (size_t)c->rows[(size_t)c->order[i]] * 64, 64 * sizeof(float));
-    }
-    for (size_t i = 0; i < n; ++i) {
-        const size_t g = (size_t)c->order[i];
-        if (positions) { positions[2 * i] = c->positions[2 * g]; positions[2 * i + 1] = c->positions[2 * g + 1]; }
-        if (scale) scale[i] = c->scale[g];
-        if (orientation) orientation[i] = c->orientation[g];
-        if (colors) std::memcpy(colors + 3 * i, c->colors.data() + 3 * g, 3);
-        if (normalized_positions) {
-            normalized_positions[2 * i] = c->normalized[2 * g];
-            normalized_positions[2 * i + 1] = c->normalized[2 * g + 1];
-        }
-    }
-    return OSFM_OK;
+    return download_features(c, "osfm_surf_download", 64, descriptors, positions, scale, orientation, colors, normalized_positions);
 }
 
 int osfm_surf_debug_image(osfm_surf *c, int octave, int sample, float *out, int32_t *width, int32_t *height)
@@ -429,16 +306,7 @@ int osfm_surf_debug_image(osfm_surf *c, int octave, int sample, float *out, int3
 
 int osfm_surf_debug_keypoints(osfm_surf *c, int after_localisation, float *out, int32_t *count)
 {
-    if (!c) { set_error("osfm_surf_debug_keypoints: null argument"); return OSFM_E_ARG; }
-    if (!c->have) { set_error("osfm_surf_debug_keypoints: no extraction"); return OSFM_E_STATE; }
-    const int n = after_localisation ? c->n_kp : c->n_cand;
-    if (count) *count = n;
-    if (!out || !n) return OSFM_OK;
-    OSFM_HIP_CHECK(hipSetDevice(c->device));
-    OSFM_HIP_CHECK(hipMemcpyAsync(out, after_localisation ? c->kps.ptr : c->cand.ptr, (size_t)n * sizeof(Keypoint),
-        hipMemcpyDeviceToHost, c->stream));
-    OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return OSFM_OK;
+    return debug_keypoints(c, "osfm_surf_debug_keypoints", after_localisation, out, count);
 }
 
 int osfm_surf_debug_describe(osfm_surf *c, float x, float y, float scale, float orientation, int upright, float *out,

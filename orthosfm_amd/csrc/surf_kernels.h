@@ -7,13 +7,13 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
-#include "sift_kernels.h"
+#include "detect_kernels.h"
 
 namespace osfm {
 namespace surf {
 
-using sift::kBlock;
-using sift::Keypoint;               // rows (octave, sample, x, y), as the SIFT stages keep them
+using detect::kBlock;
+using detect::Keypoint;             // rows (octave, sample, x, y), as the SIFT stages keep them
 
 constexpr int kOctaves = 4, kSamples = 4;
 constexpr int kOriSamples = 109;    // grid points of a circle of radius 6

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(kBlock) void extrema_kernel(const float *m0, const 
         }
     }
     int total;
-    const int rank = sift::block_rank(flag, &total);
+    const int rank = detect::block_rank(flag, &total);
     if (!WRITE) {
         if (threadIdx.x == 0) counts[block_base + blockIdx.x] = total;
     } else if (flag) {
@@ -261,7 +261,7 @@ __global__ __launch_bounds__(kBlock) void localise_kernel(MapsView mv, float con
         keep[i] = ok ? 1 : 0;
     }
     int total;
-    (void)sift::block_rank(ok, &total);
+    (void)detect::block_rank(ok, &total);
     if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 

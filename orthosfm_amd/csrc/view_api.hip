@@ -3,9 +3,9 @@
 #include <cstring>
 #include <memory>
 
+#include "detector_context.h"
 #include "feature_device.h"
 #include "feature_view.h"
-#include "osfm_common.h"
 #include "view_front.h"
 #include "view_kernels.h"
 
@@ -32,7 +32,7 @@ struct osfm_view_front {
     const uint8_t *d_image = nullptr;
     bool have_marks = false, compacted = false;
     bool host_rows_stale = false;          // compacted: the host arrays below still hold every row of the detectors
-    DeviceFeatures fs, fu;
+    const DetectorContext *fs = nullptr, *fu = nullptr;     // the detectors' results (NULL: no such detector)
     std::vector<float> h_positions, h_scale, h_orientation;     // FeatureSet's order, SIFT rows first
     std::vector<int32_t> h_sift_map, h_surf_map;
     ~osfm_view_front()
@@ -48,6 +48,8 @@ struct osfm_view_front {
 namespace {
 
 void half(int *w, int *h) { *w = (*w + 1) >> 1; *h = (*h + 1) >> 1; }
+
+const float *desc_of(const DetectorContext *f) { return f ? f->desc.as<float>() : nullptr; }
 
 // bundler::Features::compute's chain on a size: downscale_factor - 1 halvings (downscale_image), then halvings
 // while width * height > max_image_size, in int as in the reference.  False where rescale_half_size throws.
@@ -148,29 +150,22 @@ int load(osfm_view_front *c, const uint8_t *pixels, int width, int height, int c
 
     osfm_view_summary sum;
     std::memset(&sum, 0, sizeof(sum));
-    c->fs = DeviceFeatures(); c->fu = DeviceFeatures();
-    if (c->sift) {
-        OSFM_RETURN_IF(sift_extract_device(c->sift, d_image, c->ev[1], fw, fh, channels, &sum.sift));
-        OSFM_RETURN_IF(sift_device_features(c->sift, &c->fs));
-    }
-    if (c->surf) {
-        OSFM_RETURN_IF(surf_extract_device(c->surf, d_image, c->ev[1], fw, fh, channels, &sum.surf));
-        OSFM_RETURN_IF(surf_device_features(c->surf, &c->fu));
-    }
+    if (c->sift) OSFM_RETURN_IF(sift_extract_device(c->sift, d_image, c->ev[1], fw, fh, channels, &sum.sift));
+    if (c->surf) OSFM_RETURN_IF(surf_extract_device(c->surf, d_image, c->ev[1], fw, fh, channels, &sum.surf));
     OSFM_HIP_CHECK(hipSetDevice(c->device));
 
     // FeatureSet's order on the host (the detectors keep the order by scale there): a few bytes per feature go up,
     // the descriptors stay where they are
-    const int ns = c->fs.n, nu = c->fu.n, n = ns + nu;
+    const int ns = c->fs ? c->fs->n_desc : 0, nu = c->fu ? c->fu->n_desc : 0, n = ns + nu;
     if ((size_t)n > c->max_features) { set_error("osfm_view_front_load: internal: %d features exceed the arrays", n); return OSFM_E_STATE; }
     c->h_positions.resize((size_t)n * 2); c->h_scale.resize((size_t)n); c->h_orientation.resize((size_t)n);
     c->h_sift_map.resize((size_t)ns); c->h_surf_map.resize((size_t)nu);
-    auto rows = [&](const DeviceFeatures &f, int base, std::vector<int32_t> *map) {
-        for (int i = 0; i < f.n; ++i) {
-            const size_t g = (size_t)(*f.order)[(size_t)i], o = (size_t)(base + i);
-            c->h_positions[2 * o] = (*f.positions)[2 * g]; c->h_positions[2 * o + 1] = (*f.positions)[2 * g + 1];
-            c->h_scale[o] = (*f.scale)[g]; c->h_orientation[o] = (*f.orientation)[g];
-            (*map)[(size_t)i] = f.rows ? (*f.rows)[g] : (int32_t)g;
+    auto rows = [&](const DetectorContext *f, int base, std::vector<int32_t> *map) {
+        for (size_t i = 0; i < map->size(); ++i) {
+            const size_t g = (size_t)f->order[i], o = (size_t)base + i;
+            c->h_positions[2 * o] = f->positions[2 * g]; c->h_positions[2 * o + 1] = f->positions[2 * g + 1];
+            c->h_scale[o] = f->scale[g]; c->h_orientation[o] = f->orientation[g];
+            (*map)[i] = f->desc_row(g);
         }
     };
     rows(c->fs, 0, &c->h_sift_map);
@@ -232,18 +227,6 @@ int load(osfm_view_front *c, const uint8_t *pixels, int width, int height, int c
     return OSFM_OK;
 }
 
-// rows map[0..n) of a detector's descriptor array, `dim` floats each, into out
-int download_rows(osfm_view_front *c, const float *desc, const std::vector<int32_t> &map, int dim, float *out)
-{
-    if (map.empty()) return OSFM_OK;
-    const size_t last = (size_t)*std::max_element(map.begin(), map.end()) + 1;
-    std::vector<float> gen(last * dim);
-    OSFM_HIP_CHECK(hipMemcpyAsync(gen.data(), desc, gen.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < map.size(); ++i) std::memcpy(out + i * dim, gen.data() + (size_t)map[i] * dim, (size_t)dim * sizeof(float));
-    return OSFM_OK;
-}
-
 // After a load that moved the kept rows together on the device, the host's arrays follow on the first download: the
 // load itself waits for the two counts alone.
 int refresh_host_rows(osfm_view_front *c)
@@ -271,16 +254,7 @@ int check_load_args(osfm_view_front *c, const uint8_t *pixels, int width, int he
     if (!c || !pixels) { set_error("%s: null argument", who); return OSFM_E_ARG; }
     c->have = false;          // whatever comes of this call, the previous result is gone
     c->have_marks = false;
-    if (channels != 1 && channels != 3) {
-        set_error("%s: %d channels: a grey (1) or colour (3) image is expected", who, channels);
-        return OSFM_E_ARG;
-    }
-    if (width < 1 || height < 1) { set_error("%s: image size %d x %d", who, width, height); return OSFM_E_ARG; }
-    if (width > c->max_w || height > c->max_h) {
-        set_error("%s: a %d x %d image exceeds the front end's %d x %d", who, width, height, c->max_w, c->max_h);
-        return OSFM_E_RANGE;
-    }
-    return OSFM_OK;
+    return check_image(who, "front end", c->max_w, c->max_h, width, height, channels);
 }
 
 }  // namespace
@@ -293,7 +267,7 @@ int view_front_result(osfm_view_front *c, FrontResult *out)
     if (!c->have) { set_error("osfm_view_front: no load to hand off"); return OSFM_E_STATE; }
     out->device = c->device;
     const view::ViewRows rows = rows_of(c, c->compacted);
-    out->sift_desc = c->fs.desc; out->surf_desc = c->fu.desc; out->normalized = rows.normalized;
+    out->sift_desc = desc_of(c->fs); out->surf_desc = desc_of(c->fu); out->normalized = rows.normalized;
     out->sift_map = rows.sift_map; out->surf_map = rows.surf_map;
     out->n_sift = c->n_sift; out->n_surf = c->n_surf;
     return OSFM_OK;
@@ -335,18 +309,12 @@ int osfm_view_front_create(int device, int max_width, int max_height, const osfm
     osfm_view_options vo;
     (void)osfm_view_options_default(&vo);
     if (view_opts) vo = *view_opts;
-    if (max_width < 1 || max_height < 1 || max_width > 16384 || max_height > 16384) {
-        set_error("osfm_view_front_create: image size %d x %d outside 1..16384", max_width, max_height);
-        return OSFM_E_ARG;
-    }
+    OSFM_RETURN_IF(check_bounds("osfm_view_front_create", max_width, max_height));
     if (vo.downscale_factor < 1 || vo.downscale_factor > 16 || vo.feature_types < 1 || vo.feature_types > OSFM_FEATURE_ALL) {
         set_error("osfm_view_front_create: invalid options (downscale_factor 1..16, feature_types 1..3)");
         return OSFM_E_ARG;
     }
-    int ndev = 0;
-    OSFM_HIP_CHECK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) { set_error("osfm_view_front_create: device %d of %d", device, ndev); return OSFM_E_ARG; }
-    OSFM_HIP_CHECK(hipSetDevice(device));
+    OSFM_RETURN_IF(select_device("osfm_view_front_create", device));
     std::unique_ptr<osfm_view_front> c(new osfm_view_front);
     c->device = device; c->max_w = max_width; c->max_h = max_height; c->opts = vo;
     // the detectors' bound: the input bound after the fixed halvings (an image under max_image_size passes the loop
@@ -362,10 +330,12 @@ int osfm_view_front_create(int device, int max_width, int max_height, const osfm
     if (vo.feature_types & OSFM_FEATURE_SIFT) {
         OSFM_RETURN_IF(osfm_sift_create(device, dw, dh, &so, &c->sift));
         c->max_features += (size_t)so.max_keypoints;
+        c->fs = detector_of(c->sift);
     }
     if (vo.feature_types & OSFM_FEATURE_SURF) {
         OSFM_RETURN_IF(osfm_surf_create(device, dw, dh, &uo, &c->surf));
         c->max_features += (size_t)uo.max_keypoints;
+        c->fu = detector_of(c->surf);
     }
     const size_t K = c->max_features;
     OSFM_RETURN_IF(c->img[0].reserve((size_t)max_width * max_height * 3));
@@ -491,8 +461,8 @@ int osfm_view_front_download(osfm_view_front *c, float *positions, float *normal
     if (normalized && n) OSFM_HIP_CHECK(hipMemcpyAsync(normalized, rows.normalized, n * 8, hipMemcpyDeviceToHost, c->stream));
     if (colors && n) OSFM_HIP_CHECK(hipMemcpyAsync(colors, rows.colors, n * 3, hipMemcpyDeviceToHost, c->stream));
     OSFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (sift_descriptors) OSFM_RETURN_IF(download_rows(c, c->fs.desc, c->h_sift_map, 128, sift_descriptors));
-    if (surf_descriptors) OSFM_RETURN_IF(download_rows(c, c->fu.desc, c->h_surf_map, 64, surf_descriptors));
+    if (sift_descriptors) OSFM_RETURN_IF(gather_descriptors(c->stream, desc_of(c->fs), c->h_sift_map, 128, sift_descriptors));
+    if (surf_descriptors) OSFM_RETURN_IF(gather_descriptors(c->stream, desc_of(c->fu), c->h_surf_map, 64, surf_descriptors));
     return OSFM_OK;
 }
 

@@ -39,79 +39,6 @@ class Features:
         return self.descriptors.shape[0]
 
 
-class SiftExtractor:
-    """One context (osfm_sift): the pyramid and work arrays for images up to max_width x max_height.  The keyword
-    options are the fields of osfm_sift_options (Sift::Options and max_keypoints)."""
-
-    def __init__(self, device: int = 0, max_width: int = 2048, max_height: int = 2048, **opts):
-        o = capi.default_sift_options()
-        for k, v in opts.items():
-            if not hasattr(o, k):
-                raise TypeError(f"SiftExtractor: unknown option {k!r}")
-            setattr(o, k, v)
-        self.options = o
-        self.summary = None
-        self._h = C.c_void_p()
-        capi.check(capi.lib.osfm_sift_create(device, int(max_width), int(max_height), C.byref(o), C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            capi.check(capi.lib.osfm_sift_destroy(self._h))
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def run(self, image) -> capi.SiftSummary:
-        """osfm_sift_extract alone: the summary (counts and stage times); the result stays in the context."""
-        image = np.asarray(image)
-        if image.dtype != np.uint8 or image.ndim not in (2, 3):
-            raise TypeError("SiftExtractor: an uint8 image [h, w] or [h, w, channels] is expected")
-        image = np.ascontiguousarray(image)
-        channels = 1 if image.ndim == 2 else image.shape[2]
-        s = capi.SiftSummary()
-        capi.check(capi.lib.osfm_sift_extract(self._h, image.ctypes.data, image.shape[1], image.shape[0], channels, C.byref(s)))
-        self.summary = s
-        return s
-
-    def download(self) -> Features:
-        """osfm_sift_download of the last run()."""
-        n = self.summary.num_descriptors
-        f = Features(np.zeros((n, 128), np.float32), np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32),
-                     np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.uint8))
-        capi.check(capi.lib.osfm_sift_download(self._h, f.descriptors.ctypes.data, f.positions.ctypes.data, f.scale.ctypes.data,
-                                               f.orientation.ctypes.data, f.colors.ctypes.data, f.normalized.ctypes.data))
-        return f
-
-    def extract(self, image) -> Features:
-        self.run(image)
-        return self.download()
-
-    # --- test hooks ---------------------------------------------------------------------------------------------
-    def debug_image(self, octave: int, kind: int, index: int) -> np.ndarray:
-        w, h = C.c_int32(), C.c_int32()
-        capi.check(capi.lib.osfm_sift_debug_image(self._h, octave, kind, index, None, C.byref(w), C.byref(h)))
-        out = np.zeros((h.value, w.value), np.float32)
-        capi.check(capi.lib.osfm_sift_debug_image(self._h, octave, kind, index, out.ctypes.data, None, None))
-        return out
-
-    def debug_keypoints(self, after_localisation: bool) -> np.ndarray:
-        n = C.c_int32()
-        capi.check(capi.lib.osfm_sift_debug_keypoints(self._h, int(after_localisation), None, C.byref(n)))
-        out = np.zeros((n.value, 4), np.float32)
-        capi.check(capi.lib.osfm_sift_debug_keypoints(self._h, int(after_localisation), out.ctypes.data, None))
-        return out
-
-
 def _image_arg(who, image):
     image = np.asarray(image)
     if image.dtype != np.uint8 or image.ndim not in (2, 3):
@@ -120,25 +47,16 @@ def _image_arg(who, image):
     return image, 1 if image.ndim == 2 else image.shape[2]
 
 
-class SurfExtractor:
-    """One context (osfm_surf): the summed-area table, the response maps and work arrays for images up to
-    max_width x max_height.  The keyword options are the fields of osfm_surf_options (Surf::Options and
-    max_keypoints)."""
+class _Handle:
+    """The life cycle of one C context, self._h: closed once, by hand, by `with` or with the object."""
+    _prefix = None              # the C functions are osfm_<prefix>_*
 
-    def __init__(self, device: int = 0, max_width: int = 2048, max_height: int = 2048, **opts):
-        o = capi.default_surf_options()
-        for k, v in opts.items():
-            if not hasattr(o, k):
-                raise TypeError(f"SurfExtractor: unknown option {k!r}")
-            setattr(o, k, v)
-        self.options = o
-        self.summary = None
-        self._h = C.c_void_p()
-        capi.check(capi.lib.osfm_surf_create(device, int(max_width), int(max_height), C.byref(o), C.byref(self._h)))
+    def _c(self, name):
+        return getattr(capi.lib, f"osfm_{self._prefix}_{name}")
 
     def close(self):
         if self._h:
-            capi.check(capi.lib.osfm_surf_destroy(self._h))
+            capi.check(self._c("destroy")(self._h))
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -153,41 +71,76 @@ class SurfExtractor:
     def __exit__(self, *exc):
         self.close()
 
-    def run(self, image) -> capi.SurfSummary:
-        """osfm_surf_extract alone: the summary (counts and stage times); the result stays in the context."""
-        image, channels = _image_arg("SurfExtractor", image)
-        s = capi.SurfSummary()
-        capi.check(capi.lib.osfm_surf_extract(self._h, image.ctypes.data, image.shape[1], image.shape[0], channels, C.byref(s)))
+
+class _Detector(_Handle):
+    """What SiftExtractor and SurfExtractor share: one context for images up to max_width x max_height, whose keyword
+    options are the fields of the detector's options struct."""
+    _options = _summary = _width = None     # the options factory, the summary type, floats per descriptor
+
+    def __init__(self, device: int = 0, max_width: int = 2048, max_height: int = 2048, **opts):
+        o = self._options()
+        for k, v in opts.items():
+            if not hasattr(o, k):
+                raise TypeError(f"{type(self).__name__}: unknown option {k!r}")
+            setattr(o, k, v)
+        self.options = o
+        self.summary = None
+        self._h = C.c_void_p()
+        capi.check(self._c("create")(device, int(max_width), int(max_height), C.byref(o), C.byref(self._h)))
+
+    def run(self, image):
+        """osfm_*_extract alone: the summary (counts and stage times); the result stays in the context."""
+        image, channels = _image_arg(type(self).__name__, image)
+        s = self._summary()
+        capi.check(self._c("extract")(self._h, image.ctypes.data, image.shape[1], image.shape[0], channels, C.byref(s)))
         self.summary = s
         return s
 
     def download(self) -> Features:
-        """osfm_surf_download of the last run()."""
+        """osfm_*_download of the last run()."""
         n = self.summary.num_descriptors
-        f = Features(np.zeros((n, 64), np.float32), np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32),
+        f = Features(np.zeros((n, self._width), np.float32), np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32),
                      np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.uint8))
-        capi.check(capi.lib.osfm_surf_download(self._h, f.descriptors.ctypes.data, f.positions.ctypes.data, f.scale.ctypes.data,
-                                               f.orientation.ctypes.data, f.colors.ctypes.data, f.normalized.ctypes.data))
+        capi.check(self._c("download")(self._h, f.descriptors.ctypes.data, f.positions.ctypes.data, f.scale.ctypes.data,
+                                       f.orientation.ctypes.data, f.colors.ctypes.data, f.normalized.ctypes.data))
         return f
 
     def extract(self, image) -> Features:
         self.run(image)
         return self.download()
 
-    # --- test hooks ---------------------------------------------------------------------------------------------
-    def debug_image(self, octave: int, sample: int) -> np.ndarray:
+    def _debug_image(self, *plane) -> np.ndarray:
         w, h = C.c_int32(), C.c_int32()
-        capi.check(capi.lib.osfm_surf_debug_image(self._h, octave, sample, None, C.byref(w), C.byref(h)))
+        capi.check(self._c("debug_image")(self._h, *plane, None, C.byref(w), C.byref(h)))
         out = np.zeros((h.value, w.value), np.float32)
-        capi.check(capi.lib.osfm_surf_debug_image(self._h, octave, sample, out.ctypes.data, None, None))
+        capi.check(self._c("debug_image")(self._h, *plane, out.ctypes.data, None, None))
         return out
 
     def debug_keypoints(self, after_localisation: bool) -> np.ndarray:
         n = C.c_int32()
-        capi.check(capi.lib.osfm_surf_debug_keypoints(self._h, int(after_localisation), None, C.byref(n)))
+        capi.check(self._c("debug_keypoints")(self._h, int(after_localisation), None, C.byref(n)))
         out = np.zeros((n.value, 4), np.float32)
-        capi.check(capi.lib.osfm_surf_debug_keypoints(self._h, int(after_localisation), out.ctypes.data, None))
+        capi.check(self._c("debug_keypoints")(self._h, int(after_localisation), out.ctypes.data, None))
         return out
+
+
+class SiftExtractor(_Detector):
+    """One context (osfm_sift): the pyramid and work arrays for images up to max_width x max_height.  The keyword
+    options are the fields of osfm_sift_options (Sift::Options and max_keypoints)."""
+    _prefix, _options, _summary, _width = "sift", staticmethod(capi.default_sift_options), capi.SiftSummary, 128
+
+    def debug_image(self, octave: int, kind: int, index: int) -> np.ndarray:
+        return self._debug_image(octave, kind, index)
+
+
+class SurfExtractor(_Detector):
+    """One context (osfm_surf): the summed-area table, the response maps and work arrays for images up to
+    max_width x max_height.  The keyword options are the fields of osfm_surf_options (Surf::Options and
+    max_keypoints)."""
+    _prefix, _options, _summary, _width = "surf", staticmethod(capi.default_surf_options), capi.SurfSummary, 64
+
+    def debug_image(self, octave: int, sample: int) -> np.ndarray:
+        return self._debug_image(octave, sample)
 
     def debug_describe(self, x, y, scale, orientation, upright=False):
         """(descriptor [64], status) of one hand-placed descriptor on the last image: status 0 rejected, 1 ok,
@@ -280,10 +233,11 @@ def mark_rows_host(normalized, image, mask=None, clamp="reference", threshold=16
     return xy, rgb, mark
 
 
-class ViewFrontEnd:
+class ViewFrontEnd(_Handle):
     """One context (osfm_view_front) for images up to max_width x max_height: image in host memory -> halving
     chain -> SIFT and SURF from one upload -> colours and normalised positions, all on the device.  `sift` and
     `surf` are dictionaries of the detectors' options."""
+    _prefix = "view_front"
 
     def __init__(self, device: int = 0, max_width: int = 2048, max_height: int = 2048, downscale_factor: int = 1,
                  max_image_size: int = 6_000_000, feature_types: int = capi.FEATURE_ALL, sift=None, surf=None):
@@ -298,23 +252,6 @@ class ViewFrontEnd:
         self._h = C.c_void_p()
         capi.check(capi.lib.osfm_view_front_create(device, int(max_width), int(max_height), C.byref(vo), C.byref(so), C.byref(uo),
                                                    C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            capi.check(capi.lib.osfm_view_front_destroy(self._h))
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def load(self, image) -> capi.ViewSummary:
         """osfm_view_front_load: the summary (sizes, counts, stage times); the result stays on the device for
