@@ -865,9 +865,25 @@ OSFM_API int osfm_tracks_select_observations(int64_t num_features, const int32_t
  * out: groups [max_groups][group_size] view ids, group_tracks [max_groups]
  * (ViewGroup::tracks), *num_groups.  A score is the number of tracks holding
  * every view of the group (bitset popcounts on the device); candidates are taken
- * in ascending id order on ties (the reference's OpenMP loop leaves ties to
- * thread timing).  OSFM_E_STATE when a remaining view shares no track with any
- * seed group (the reference never terminates there). */
+ * in ascending id order on ties, the first seed in lexicographic order among
+ * seeds (the reference's OpenMP loop leaves ties to thread timing).
+ * Precondition: no track holds a view twice (Tracks::remove_invalid_tracks has
+ * run).  Such a track counts once for that view here, while the reference
+ * counts features, so e.g. [1, 1, 2] is a full track of the group {1, 2, 4} to it.
+ * OSFM_E_ARG (*num_groups untouched): null arrays, num_views < 2, duplicate ids,
+ * group_size outside [3, 8].  OSFM_E_CAPACITY: more than max_groups groups; the
+ * first max_groups are written.  OSFM_E_STATE, with the groups found until then
+ * and their number in *num_groups:
+ *   - a pick scores 0, i.e. a remaining view shares no track with any seed
+ *     group.  The reference appends bestViewID's start value, view id 0, there:
+ *     it goes on if id 0 is a view still unassigned (ids [4, 7, 0, 9] with
+ *     tracks over 4, 7 and 9 only give it [4, 7, 9], [4, 7, 0] with 2 and 0
+ *     tracks) and never terminates otherwise.  Here the call is refused in
+ *     both cases.
+ *   - num_views == 2, for which the reference returns the one group
+ *     [v0, v1, 0] with 0 tracks.
+ * OSFM_GROUPS_GENERAL in the environment (read on every call) sends group size
+ * 3 down the general path of the other sizes instead of its incremental form. */
 OSFM_API int osfm_build_groups(int device, int32_t num_views, const int32_t *view_ids,
     int32_t num_tracks, const int64_t *track_offsets, const int32_t *track_views,
     int32_t group_size, int32_t max_groups, int32_t *groups, int32_t *group_tracks,

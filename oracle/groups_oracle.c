@@ -19,7 +19,15 @@
  * Output: groups [max_groups][group_size] ids, group_tracks [max_groups]
  * (ViewGroup::tracks); returns the number of groups, or -1 when the loop cannot
  * make progress (the reference would spin forever: a remaining view shares no
- * track with any seed) or max_groups is too small.
+ * track with any seed, and the view id 0 that it appends then is not an
+ * unassigned view) or max_groups is too small.
+ *
+ * Kept literal where the product (osfm_build_groups) decides otherwise: when
+ * nothing scores, bestViewID's start value 0 is appended, and the loop goes on
+ * if id 0 was still unassigned (the product refuses); num_views == 2 gives the
+ * one group [v0, v1, 0] with 0 tracks (refused there); a track that holds a view
+ * twice is counted per feature (once per view there; such tracks are excluded
+ * by the product's precondition).
  */
 #include <stdint.h>
 #include <stdlib.h>

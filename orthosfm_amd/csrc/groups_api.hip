@@ -18,6 +18,7 @@
 // timing (group.cpp:118-146).
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <vector>
@@ -42,7 +43,13 @@ group_score_kernel(const uint64_t *__restrict__ bt, int V, int W, const int32_t 
     __shared__ int32_t s_idx[kGroupThreads];
     const int s = blockIdx.x, tid = threadIdx.x;
     int sv[kMaxGroup];
-    for (int j = 0; j < n_seed; ++j) sv[j] = seeds[(size_t)s * n_seed + j];
+    // a seed whose earlier step found no candidate carries -1 there (first group of sizes >= 4): it
+    // stays without a pick, and -1 must not index the bitsets
+    bool dead = false;
+    for (int j = 0; j < n_seed; ++j) {
+        sv[j] = seeds[(size_t)s * n_seed + j];
+        if (sv[j] < 0) { dead = true; sv[j] = 0; }
+    }
     uint32_t my_best = 0;
     int32_t my_idx = -1;
     for (int r0 = 0; r0 < R; r0 += kGroupThreads) {
@@ -57,7 +64,7 @@ group_score_kernel(const uint64_t *__restrict__ bt, int V, int W, const int32_t 
         }
         bool in_seed = false;
         for (int j = 0; j < n_seed; ++j) in_seed |= sv[j] == c;        // group.cpp:123-125
-        if (r < R && !in_seed && acc > my_best) { my_best = acc; my_idx = r; }   // strictly better, ascending r
+        if (r < R && !dead && !in_seed && acc > my_best) { my_best = acc; my_idx = r; }   // strictly better, ascending r
     }
     s_score[tid] = my_best; s_idx[tid] = my_idx;
     __syncthreads();
@@ -186,7 +193,6 @@ int osfm_build_groups(int device, int32_t num_views, const int32_t *view_ids, in
         set_error("build_groups: group size %d outside [3, %d] (the reference's algorithms use 3)", group_size, kMaxGroup);
         return OSFM_E_ARG;
     }
-    *num_groups = 0;
     const int V = num_views;
     // ranks by ascending id: internal index order == id order (std::set / std::sort in the reference)
     std::vector<int> by_id(V);
@@ -196,6 +202,7 @@ int osfm_build_groups(int device, int32_t num_views, const int32_t *view_ids, in
     for (int r = 0; r < V; ++r) {
         if (!rank_of.insert({view_ids[by_id[r]], r}).second) { set_error("build_groups: duplicate view id"); return OSFM_E_ARG; }
     }
+    *num_groups = 0;                                    // OSFM_E_ARG leaves it as the caller set it
     // bitsets over the tracks, transposed
     const int W = std::max(1, (num_tracks + 63) / 64);
     std::vector<uint64_t> bt((size_t)W * V, 0);
@@ -204,8 +211,14 @@ int osfm_build_groups(int device, int32_t num_views, const int32_t *view_ids, in
             auto it = rank_of.find(track_views[k]);
             if (it != rank_of.end()) bt[(size_t)(t >> 6) * V + it->second] |= 1ull << (t & 63);
         }
+    if (V == 2) {
+        // the reference returns [v0, v1, 0] with 0 tracks (bestViewID's start value); a group needs a third view
+        set_error("build_groups: two views do not make a group (the reference emits [v0, v1, 0] with 0 tracks)");
+        return OSFM_E_STATE;
+    }
     OSFM_HIP_CHECK(hipSetDevice(device));
-    if (group_size == 3) {
+    const bool force_general = getenv("OSFM_GROUPS_GENERAL") != nullptr;      // read on every call (A/B runs and tests)
+    if (group_size == 3 && !force_general) {
         // ---- incremental form (see the kernels above) --------------------------
         const size_t P = (size_t)V * (V - 1) / 2;
         const size_t rows_bytes = P * (size_t)V * 4;
