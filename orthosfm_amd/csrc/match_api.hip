@@ -417,33 +417,38 @@ int osfm_ransac_options_default(osfm_ransac_options *o)
     return OSFM_OK;
 }
 
-int osfm_ransac_fundamental(int device, const float *pos1, int n1, const float *pos2, int n2,
-    const int32_t *corr, int k, const osfm_ransac_options *opts, uint64_t pair_id,
-    int32_t *inliers, int32_t *num_inliers, double *F)
+}  // extern "C"
+
+// One pair through a pair-RANSAC kernel, for the two single-pair entries: the checks, the upload, the job record, the
+// launch (launch(job, scratch, result record), all on the device), the wait and the results.  name: the entry in
+// error messages; min_k: the matches a sample of the model needs; result: the model's own record, if it has one.
+template <class Launch>
+static int ransac_single_pair(const char *name, int min_k, size_t scratch_bytes, int device, const float *pos1, int n1,
+    const float *pos2, int n2, const int32_t *corr, int k, uint64_t pair_id, int32_t *inliers, int32_t *num_inliers,
+    double *F, void *result, size_t result_bytes, Launch launch)
 {
     if (n1 < 0 || n2 < 0 || k < 0 || !num_inliers || (k > 0 && (!pos1 || !pos2 || !corr || !inliers))) {
-        set_error("ransac_fundamental: bad argument"); return OSFM_E_ARG;
+        set_error("%s: bad argument", name); return OSFM_E_ARG;
     }
     for (int i = 0; i < k; ++i)
         if (corr[2 * i] < 0 || corr[2 * i] >= n1 || corr[2 * i + 1] < 0 || corr[2 * i + 1] >= n2) {
-            set_error("ransac_fundamental: correspondence %d out of range", i); return OSFM_E_ARG;
+            set_error("%s: correspondence %d out of range", name, i); return OSFM_E_ARG;
         }
-    osfm_ransac_options o;
-    if (opts) o = *opts; else osfm_ransac_options_default(&o);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("ransac_fundamental: no HIP device available (this backend has no CPU fallback)");
+        set_error("%s: no HIP device available (this backend has no CPU fallback)", name);
         return OSFM_E_DEVICE;
     }
-    if (device < 0 || device >= ndev) { set_error("ransac_fundamental: bad device"); return OSFM_E_ARG; }
+    if (device < 0 || device >= ndev) { set_error("%s: bad device", name); return OSFM_E_ARG; }
     OSFM_HIP_CHECK(hipSetDevice(device));
-    if (k < 8) { *num_inliers = -1; return OSFM_OK; }
-    DeviceBuffer d1, d2, dc, di, dn, df, dj;
-    struct Rel { DeviceBuffer *b[7]; ~Rel() { for (auto *x : b) x->release(); } } rel{{&d1, &d2, &dc, &di, &dn, &df, &dj}};
+    if (k < min_k) { *num_inliers = -1; return OSFM_OK; }
+    DeviceBuffer d1, d2, dc, di, dn, df, dj, dr;
+    struct Rel { DeviceBuffer *b[8]; ~Rel() { for (auto *x : b) x->release(); } } rel{{&d1, &d2, &dc, &di, &dn, &df, &dj, &dr}};
     OSFM_RETURN_IF(d1.reserve((size_t)n1 * 8)); OSFM_RETURN_IF(d2.reserve((size_t)n2 * 8));
     OSFM_RETURN_IF(dc.reserve((size_t)k * 8)); OSFM_RETURN_IF(di.reserve((size_t)k * 4));
     OSFM_RETURN_IF(dn.reserve(16)); OSFM_RETURN_IF(df.reserve(72));
-    OSFM_RETURN_IF(dj.reserve(256 + ransac_scratch_bytes(1)));       // the job, then the kernel's scratch
+    if (result_bytes) OSFM_RETURN_IF(dr.reserve(result_bytes));
+    OSFM_RETURN_IF(dj.reserve(256 + scratch_bytes));                 // the job, then the kernel's scratch
     OSFM_HIP_CHECK(hipMemcpy(d1.ptr, pos1, (size_t)n1 * 8, hipMemcpyHostToDevice));
     OSFM_HIP_CHECK(hipMemcpy(d2.ptr, pos2, (size_t)n2 * 8, hipMemcpyHostToDevice));
     OSFM_HIP_CHECK(hipMemcpy(dc.ptr, corr, (size_t)k * 8, hipMemcpyHostToDevice));
@@ -453,7 +458,7 @@ int osfm_ransac_fundamental(int device, const float *pos1, int n1, const float *
     job.pair_id = pair_id; job.inliers_out = di.as<int32_t>(); job.count_out = dn.as<int32_t>();
     job.F_out = df.as<double>();
     OSFM_HIP_CHECK(hipMemcpy(dj.ptr, &job, sizeof(job), hipMemcpyHostToDevice));
-    launch_ransac(dj.as<RansacJob>(), 1, o.max_iterations, o.threshold, o.seed, static_cast<char *>(dj.ptr) + 256, nullptr);
+    launch(dj.as<RansacJob>(), static_cast<char *>(dj.ptr) + 256, dr.ptr);
     OSFM_HIP_CHECK(hipGetLastError());
     OSFM_HIP_CHECK(hipDeviceSynchronize());
     int32_t cnt = 0;
@@ -461,7 +466,22 @@ int osfm_ransac_fundamental(int device, const float *pos1, int n1, const float *
     *num_inliers = cnt;
     if (cnt > 0) OSFM_HIP_CHECK(hipMemcpy(inliers, di.ptr, (size_t)cnt * 4, hipMemcpyDeviceToHost));
     if (F) OSFM_HIP_CHECK(hipMemcpy(F, df.ptr, 72, hipMemcpyDeviceToHost));
+    if (result) OSFM_HIP_CHECK(hipMemcpy(result, dr.ptr, result_bytes, hipMemcpyDeviceToHost));
     return OSFM_OK;
+}
+
+extern "C" {
+
+int osfm_ransac_fundamental(int device, const float *pos1, int n1, const float *pos2, int n2,
+    const int32_t *corr, int k, const osfm_ransac_options *opts, uint64_t pair_id,
+    int32_t *inliers, int32_t *num_inliers, double *F)
+{
+    osfm_ransac_options o;
+    if (opts) o = *opts; else osfm_ransac_options_default(&o);
+    return ransac_single_pair("ransac_fundamental", 8, ransac_scratch_bytes(1), device, pos1, n1, pos2, n2, corr, k, pair_id,
+        inliers, num_inliers, F, nullptr, 0, [&](const RansacJob *d_job, void *scratch, void *) {
+            launch_ransac(d_job, 1, o.max_iterations, o.threshold, o.seed, scratch, nullptr);
+        });
 }
 
 int osfm_ransac_affine_options_default(osfm_ransac_affine_options *o)
@@ -475,49 +495,13 @@ int osfm_ransac_affine(int device, const float *pos1, int n1, const float *pos2,
     const int32_t *corr, int k, const osfm_ransac_affine_options *opts, uint64_t pair_id,
     int32_t *inliers, int32_t *num_inliers, double *F, osfm_ransac_affine_result *result)
 {
-    if (n1 < 0 || n2 < 0 || k < 0 || !num_inliers || (k > 0 && (!pos1 || !pos2 || !corr || !inliers))) {
-        set_error("ransac_affine: bad argument"); return OSFM_E_ARG;
-    }
-    for (int i = 0; i < k; ++i)
-        if (corr[2 * i] < 0 || corr[2 * i] >= n1 || corr[2 * i + 1] < 0 || corr[2 * i + 1] >= n2) {
-            set_error("ransac_affine: correspondence %d out of range", i); return OSFM_E_ARG;
-        }
     osfm_ransac_affine_options o;
     if (opts) o = *opts; else osfm_ransac_affine_options_default(&o);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("ransac_affine: no HIP device available (this backend has no CPU fallback)");
-        return OSFM_E_DEVICE;
-    }
-    if (device < 0 || device >= ndev) { set_error("ransac_affine: bad device"); return OSFM_E_ARG; }
-    OSFM_HIP_CHECK(hipSetDevice(device));
-    if (k < 4) { *num_inliers = -1; return OSFM_OK; }
-    DeviceBuffer d1, d2, dc, di, dn, df, dj, dr;
-    struct Rel { DeviceBuffer *b[8]; ~Rel() { for (auto *x : b) x->release(); } } rel{{&d1, &d2, &dc, &di, &dn, &df, &dj, &dr}};
-    OSFM_RETURN_IF(d1.reserve((size_t)n1 * 8)); OSFM_RETURN_IF(d2.reserve((size_t)n2 * 8));
-    OSFM_RETURN_IF(dc.reserve((size_t)k * 8)); OSFM_RETURN_IF(di.reserve((size_t)k * 4));
-    OSFM_RETURN_IF(dn.reserve(16)); OSFM_RETURN_IF(df.reserve(72)); OSFM_RETURN_IF(dr.reserve(sizeof(osfm_ransac_affine_result)));
-    OSFM_RETURN_IF(dj.reserve(256 + affine_scratch_bytes(1)));       // the job, then the kernel's scratch
-    OSFM_HIP_CHECK(hipMemcpy(d1.ptr, pos1, (size_t)n1 * 8, hipMemcpyHostToDevice));
-    OSFM_HIP_CHECK(hipMemcpy(d2.ptr, pos2, (size_t)n2 * 8, hipMemcpyHostToDevice));
-    OSFM_HIP_CHECK(hipMemcpy(dc.ptr, corr, (size_t)k * 8, hipMemcpyHostToDevice));
-    RansacJob job;
-    memset(&job, 0, sizeof(job));
-    job.pos1 = d1.as<float>(); job.pos2 = d2.as<float>(); job.corr = dc.as<int32_t>(); job.k = k;
-    job.pair_id = pair_id; job.inliers_out = di.as<int32_t>(); job.count_out = dn.as<int32_t>();
-    job.F_out = df.as<double>();
-    OSFM_HIP_CHECK(hipMemcpy(dj.ptr, &job, sizeof(job), hipMemcpyHostToDevice));
-    launch_ransac_affine(dj.as<RansacJob>(), 1, o.max_iterations, o.threshold, o.refit, o.seed, static_cast<char *>(dj.ptr) + 256,
-        dr.as<osfm_ransac_affine_result>(), nullptr);
-    OSFM_HIP_CHECK(hipGetLastError());
-    OSFM_HIP_CHECK(hipDeviceSynchronize());
-    int32_t cnt = 0;
-    OSFM_HIP_CHECK(hipMemcpy(&cnt, dn.ptr, 4, hipMemcpyDeviceToHost));
-    *num_inliers = cnt;
-    if (cnt > 0) OSFM_HIP_CHECK(hipMemcpy(inliers, di.ptr, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-    if (F) OSFM_HIP_CHECK(hipMemcpy(F, df.ptr, 72, hipMemcpyDeviceToHost));
-    if (result) OSFM_HIP_CHECK(hipMemcpy(result, dr.ptr, sizeof(*result), hipMemcpyDeviceToHost));
-    return OSFM_OK;
+    return ransac_single_pair("ransac_affine", 4, affine_scratch_bytes(1), device, pos1, n1, pos2, n2, corr, k, pair_id,
+        inliers, num_inliers, F, result, sizeof(*result), [&](const RansacJob *d_job, void *scratch, void *d_result) {
+            launch_ransac_affine(d_job, 1, o.max_iterations, o.threshold, o.refit, o.seed, scratch,
+                static_cast<osfm_ransac_affine_result *>(d_result), nullptr);
+        });
 }
 
 int osfm_match_pair(osfm_matcher *m, int view_1, int view_2, int32_t *m12, int32_t *len12,

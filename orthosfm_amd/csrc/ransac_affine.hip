@@ -9,33 +9,32 @@
 // least-squares refit on the winner's inliers.  The reference project has no such estimator (its RansacFundamental
 // is the 8-point one); the mode is opt-in (osfm_match_options.ransac_model, osfm_ransac_affine).
 //
-// Same job records, same counter-based sample stream, same split of a pair's hypotheses over kRansacSplit workgroups
-// with best-of-part slots and a last-arriver finish as ransac_kernel; no workgroup waits for another.  All arithmetic
-// is double precision in ONE operation order (this file is built without FMA contraction), restated operation for
-// operation in tests/affine_restatement.py, which the kernel equals bit for bit.  Everything a thread holds is
-// statically indexed (the elimination, the sample, the 4 x 4 Jacobi are unrolled on scalars): no scratch memory.
+// The job records, the split of a pair's hypotheses over kRansacSplit workgroups, the tie rule, the election of the
+// winner and the inlier list are the scaffold of ransac_pair.h, shared with ransac_kernel; the sample stream is that
+// of ransac_rand.h.  All arithmetic is double precision in ONE operation order (this file is built without FMA
+// contraction), restated operation for operation in tests/affine_restatement.py, which the kernel equals bit for
+// bit.  Everything a thread holds is statically indexed (the elimination, the sample, the 4 x 4 Jacobi are unrolled
+// on scalars): no scratch memory.
 #include "ransac_affine.h"
+#include "ransac_pair.h"
 #include "ransac_rand.h"
 #include "osfm_common.h"
 
-#include <algorithm>
-
 namespace osfm {
 
-// best (count, iteration, vector) of one part of a pair's hypotheses
-struct AffineSlot { int32_t count, iter; double v[5]; };
+using AffineSlot = RansacSlot<5>;
 
 namespace {
 
 // One hypothesis as the kernel holds it: v = (a, b, c, d, e), s = a^2 + b^2 + c^2 + d^2 and the two bounds of the
-// safe product tests, s thr^2 (1 -+ 2^-49) (sampson_below in ransac_kernels.hip has the argument).
+// safe product tests, s times the band's (sampson_below in ransac_kernels.hip has the argument).
 struct AffineHyp { double v[5], s, s_lo, s_hi; };
 
-__device__ __forceinline__ void affine_bounds(AffineHyp &h, double thr_lo, double thr_hi)
+__device__ __forceinline__ void affine_bounds(AffineHyp &h, const RansacBand &band)
 {
     h.s = ((h.v[0] * h.v[0] + h.v[1] * h.v[1]) + h.v[2] * h.v[2]) + h.v[3] * h.v[3];
-    h.s_lo = h.s * thr_lo;
-    h.s_hi = h.s * thr_hi;
+    h.s_lo = h.s * band.thr_lo;
+    h.s_hi = h.s * band.thr_hi;
 }
 
 // sampson(F_A, x1, y1, x2, y2) < thr2 of ransac_kernels.hip in its own order of operations, with the terms that F_A's
@@ -169,13 +168,6 @@ __device__ __forceinline__ void eig4_fixed(double (&A)[4][4], double (&V)[4][4],
     for (int i = 0; i < 4; ++i) w[i] = A[i][i];
 }
 
-// (x1, y1, x2, y2) of match i of a job
-__device__ __forceinline__ double4 load_match(const RansacJob &job, int i)
-{
-    const int a = job.corr[2 * i], b = job.corr[2 * i + 1];
-    return make_double4(job.pos1[2 * a], job.pos1[2 * a + 1], job.pos2[2 * b], job.pos2[2 * b + 1]);
-}
-
 // red[q * 256 + tid], q < N, holds a partial sum per thread: the fixed tree that leaves the totals in red[q * 256]
 template <int N>
 __device__ __forceinline__ void tree_sum(double *red, int tid)
@@ -197,9 +189,8 @@ ransac_affine_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_i
     uint64_t seed, AffineSlot *__restrict__ slots, int32_t *__restrict__ done, osfm_ransac_affine_result *__restrict__ results)
 {
     __shared__ double4 mpt[kAffineChunk];     // (x1, y1, x2, y2) of the staged matches; the partial sums of the refit
-    __shared__ int s_count[256], s_iter[256];
-    __shared__ double s_v[5];
-    __shared__ int s_wave[4], s_run, s_last, s_n;
+    __shared__ RansacLds<5> lds;
+    __shared__ int s_n;                       // inliers of the refit
 
     const int jid = blockIdx.x / kRansacSplit, part = blockIdx.x % kRansacSplit;
     const RansacJob job = jobs[jid];
@@ -210,14 +201,12 @@ ransac_affine_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_i
     }
     // this part's iterations: whole passes of 256 * kAffineHyp
     constexpr int kPass = 256 * kAffineHyp;
-    const int per_part = ((max_iterations + kRansacSplit - 1) / kRansacSplit + kPass - 1) / kPass * kPass;
-    const int it_begin = part * per_part, it_end = min(max_iterations, it_begin + per_part);
-    const double thr_lo = thr2 * (1.0 - 1.7763568394002505e-15);     // 2^-49
-    const double thr_hi = thr2 * (1.0 + 1.7763568394002505e-15);
+    const RansacRange its = ransac_part_range(max_iterations, part, kPass);
+    const RansacBand band(thr2);
     int best_count = 0, best_iter = 0x7fffffff;
     double bestv[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 
-    for (int base = it_begin; base < it_end; base += kPass) {
+    for (int base = its.begin; base < its.end; base += kPass) {
         AffineHyp H[kAffineHyp];
         bool valid[kAffineHyp];
         int cnt[kAffineHyp];
@@ -227,7 +216,7 @@ ransac_affine_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_i
             valid[h] = false; cnt[h] = 0;
 #pragma unroll
             for (int i = 0; i < 5; ++i) H[h].v[i] = 0.0;
-            if (it < it_end) {
+            if (it < its.end) {
                 // the first 4 distinct draws mod k, ascending
                 int i0 = -1, i1 = -1, i2 = -1, i3 = -1, n = 0;
                 for (uint64_t d = 0; n < 4; ++d) {
@@ -242,7 +231,7 @@ ransac_affine_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_i
                                          { m2.z, m2.w, m2.x, m2.y }, { m3.z, m3.w, m3.x, m3.y } };
                 valid[h] = four_point(P, H[h].v);
             }
-            affine_bounds(H[h], thr_lo, thr_hi);
+            affine_bounds(H[h], band);
         }
         // inlier counts of this thread's hypotheses over all matches; every lane reads the same match
         for (int c0 = 0; c0 < k; c0 += kAffineChunk) {
@@ -272,69 +261,27 @@ ransac_affine_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_i
 #pragma unroll
         for (int h = 0; h < kAffineHyp; ++h) {
             const int it = base + h * 256 + tid;
-            // strictly more inliers wins; equal non-zero counts keep the earlier iteration
-            if (valid[h] && (cnt[h] > best_count || (cnt[h] == best_count && cnt[h] > 0 && it < best_iter))) {
+            if (valid[h] && ransac_better(cnt[h], it, best_count, best_iter)) {
                 best_count = cnt[h]; best_iter = it;
 #pragma unroll
                 for (int i = 0; i < 5; ++i) bestv[i] = H[h].v[i];
             }
         }
     }
-    // block argmax: (count desc, iteration asc)
-    s_count[tid] = best_count; s_iter[tid] = best_iter;
-    __syncthreads();
-    for (int st = 128; st >= 1; st >>= 1) {
-        if (tid < st) {
-            const int c2 = s_count[tid + st], i2 = s_iter[tid + st];
-            if (c2 > s_count[tid] || (c2 == s_count[tid] && i2 < s_iter[tid])) { s_count[tid] = c2; s_iter[tid] = i2; }
-        }
-        __syncthreads();
-    }
-    int win_count = s_count[0], win_iter = s_iter[0];
-    if (best_count == win_count && best_iter == win_iter && win_count > 0) {
-#pragma unroll
-        for (int i = 0; i < 5; ++i) s_v[i] = bestv[i];
-    }
-    __syncthreads();
-    // this part's best into its slot; the last part to get here goes on with all of them
-    if (tid == 0) {
-        AffineSlot &mine = slots[(size_t)jid * kRansacSplit + part];
-        mine.count = win_count; mine.iter = win_iter;
-        for (int i = 0; i < 5; ++i) mine.v[i] = win_count > 0 ? s_v[i] : 0.0;
-        __threadfence();
-        s_last = atomicAdd(&done[jid], 1) == kRansacSplit - 1;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    if (tid == 0) {
-        __threadfence();
-        int bc = 0, bi = 0x7fffffff, bp = -1;
-        for (int p = 0; p < kRansacSplit; ++p) {
-            const AffineSlot &sl = slots[(size_t)jid * kRansacSplit + p];
-            if (sl.count > bc || (sl.count == bc && sl.count > 0 && sl.iter < bi)) { bc = sl.count; bi = sl.iter; bp = p; }
-        }
-        s_count[0] = bc; s_iter[0] = bi;
-        for (int i = 0; i < 5; ++i) s_v[i] = bp >= 0 ? slots[(size_t)jid * kRansacSplit + bp].v[i] : 0.0;
-        done[jid] = 0;                 // ready for the next launch
-        s_run = 0; s_n = 0;
-    }
-    __syncthreads();
-    win_count = s_count[0]; win_iter = s_iter[0];
+    int win_count, win_iter;
+    AffineHyp W;
+    if (!ransac_elect(lds, slots, done, jid, part, tid, best_count, best_iter, bestv, win_count, win_iter, W.v)) return;
     if (win_count == 0) {
         if (tid == 0) {
-            *job.count_out = 0;
-            if (job.F_out) for (int i = 0; i < 9; ++i) job.F_out[i] = 0.0;
+            ransac_no_winner(job);
             if (results) results[jid] = osfm_ransac_affine_result{-1, 0, 0, 0};
         }
         return;
     }
-    AffineHyp W;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) W.v[i] = s_v[i];
-    affine_bounds(W, thr_lo, thr_hi);
-    const int lane = tid & 63, wave = tid >> 6;
+    affine_bounds(W, band);
     int ran = 0, accepted = 0;
     if (refit && win_count >= 5) {
+        if (tid == 0) s_n = 0;         // added to behind the barriers of the tree sums
         // One least-squares refit on the winner's inliers: z = (x2, y2, x1, y1), the mean in a first pass, the scatter
         // about it in a second, (a, b, c, d) the scatter's eigenvector of the smallest eigenvalue, e = -(a, b, c, d) . mean.
         // Thread t adds matches t, t + 256, ... in order (a match that is no inlier adds +0), then a fixed tree over
@@ -379,7 +326,7 @@ ransac_affine_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_i
 #pragma unroll
         for (int q = 0; q < 4; ++q) R.v[q] = m == 0 ? V[q][0] : m == 1 ? V[q][1] : m == 2 ? V[q][2] : V[q][3];
         R.v[4] = -(((R.v[0] * mu0 + R.v[1] * mu1) + R.v[2] * mu2) + R.v[3] * mu3);
-        affine_bounds(R, thr_lo, thr_hi);
+        affine_bounds(R, band);
         // all matches counted again under the refit; it replaces the winner when it holds at least as many
         int mine = 0;
         for (int i = tid; i < k; i += 256) {
@@ -399,38 +346,20 @@ ransac_affine_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_i
         if (results) results[jid] = osfm_ransac_affine_result{win_iter, win_count, ran, accepted};
     }
     // ordered list of the inlier ids under the final F_A
-    for (int c0 = 0; c0 < k; c0 += 256) {
-        const int i = c0 + tid;
-        bool in = false;
-        if (i < k) {
-            const double4 m = load_match(job, i);
-            in = affine_below(W, m.x, m.y, m.z, m.w, thr2);
-        }
-        const unsigned long long bal = __ballot(in);
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int off = s_run;
-        for (int wv = 0; wv < wave; ++wv) off += s_wave[wv];
-        if (in) job.inliers_out[off + __popcll(bal & ((1ull << lane) - 1ull))] = i;
-        __syncthreads();
-        if (tid == 0) s_run += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
-    }
-    if (tid == 0) *job.count_out = s_run;
+    ransac_list_inliers(lds, job, tid, [&](int i) {
+        const double4 m = load_match(job, i);
+        return affine_below(W, m.x, m.y, m.z, m.w, thr2);
+    });
 }
 
-size_t affine_scratch_bytes(int num_jobs)
-{
-    return (size_t)std::max(num_jobs, 1) * (kRansacSplit * sizeof(AffineSlot) + 16);
-}
+size_t affine_scratch_bytes(int num_jobs) { return ransac_scratch_bytes(num_jobs, sizeof(AffineSlot)); }
 
 void launch_ransac_affine(const RansacJob *d_jobs, int num_jobs, int max_iterations, double threshold, int refit,
     uint64_t seed, void *scratch, osfm_ransac_affine_result *d_results, hipStream_t s)
 {
     if (num_jobs <= 0) return;
     AffineSlot *slots = static_cast<AffineSlot *>(scratch);
-    int32_t *done = reinterpret_cast<int32_t *>(static_cast<char *>(scratch) + (size_t)num_jobs * kRansacSplit * sizeof(AffineSlot));
-    (void)hipMemsetAsync(done, 0, (size_t)num_jobs * sizeof(int32_t), s);
+    int32_t *done = ransac_scratch_done(scratch, num_jobs, sizeof(AffineSlot), s);
     hipLaunchKernelGGL(ransac_affine_kernel, dim3(num_jobs * kRansacSplit), dim3(256), 0, s, d_jobs, num_jobs, max_iterations,
         threshold * threshold, refit != 0 ? 1 : 0, seed, slots, done, d_results);
 }

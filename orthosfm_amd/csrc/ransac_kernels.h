@@ -14,7 +14,7 @@ struct RansacJob {
     int32_t pad_;
     uint64_t pair_id;         // random stream of the pair
     int32_t *inliers_out;     // [k] ids into corr of the inliers of the best hypothesis
-    int32_t *count_out;       // number of inliers (-1: fewer than 8 matches)
+    int32_t *count_out;       // number of inliers (-1: fewer matches than a sample of the model, 8 or 4)
     double *F_out;            // [9] or null
 };
 

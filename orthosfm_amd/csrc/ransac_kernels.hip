@@ -13,11 +13,9 @@
 #include <atomic>
 #include <mutex>
 
-#include "ransac_kernels.h"
+#include "ransac_pair.h"
 #include "ransac_rand.h"
 #include "osfm_common.h"
-
-#include <algorithm>
 
 namespace osfm {
 
@@ -43,10 +41,9 @@ sampson(const double *F, double x1, double y1, double x2, double y2)
 // n >= sum * thr2 (1 + 2^-49) implies fl(n / sum) >= thr2 (the roundings of the
 // products and of the quotient, 2^-53 each, cannot bridge 2^-49); only the
 // sliver in between takes the reference's division (fundamental.cc:245).  Same
-// decisions as the oracle, bit for bit.  thr_lo / thr_hi are those two bounds.
+// decisions as the oracle, bit for bit.  The band holds thr2 and those two bounds.
 __device__ __forceinline__ bool
-sampson_below(const double *F, double x1, double y1, double x2, double y2, double thr2,
-    double thr_lo, double thr_hi)
+sampson_below(const double *F, double x1, double y1, double x2, double y2, const RansacBand &band)
 {
     const double a = x1 * F[0] + y1 * F[1] + F[2];
     const double b = x1 * F[3] + y1 * F[4] + F[5];
@@ -61,9 +58,9 @@ sampson_below(const double *F, double x1, double y1, double x2, double y2, doubl
     sum += b * b;
     t = x2 * F[0] + y2 * F[3] + F[6]; sum += t * t;
     t = x2 * F[1] + y2 * F[4] + F[7]; sum += t * t;
-    if (n < sum * thr_lo) return true;                    // strict: sum == 0 never passes here
-    if (n >= sum * thr_hi) return false;                  // 0/0 and x/0 of the reference: not below
-    return n / sum < thr2;                                // the sliver, and NaN operands
+    if (n < sum * band.thr_lo) return true;               // strict: sum == 0 never passes here
+    if (n >= sum * band.thr_hi) return false;             // 0/0 and x/0 of the reference: not below
+    return n / sum < band.thr2;                           // the sliver, and NaN operands
 }
 
 __device__ void eig3_fixed(double A[3][3], double V[3][3], double w[3])
@@ -246,23 +243,18 @@ constexpr int kChunk = 1024;       // matches staged in LDS at a time
 // of the bench (1225 workgroups, two resident per CU) ran as 2.4 waves of workgroups, the
 // last one 40 % full.  Every part keeps its best (count, iteration, F) in a slot; the part
 // that finishes last (a counter per pair) picks the overall best and lists its inliers.
-struct RansacSlot { int32_t count, iter; double F[9]; };
+using FundSlot = RansacSlot<9>;
 
-size_t ransac_scratch_bytes(int num_jobs)
-{
-    return (size_t)std::max(num_jobs, 1) * (kRansacSplit * sizeof(RansacSlot) + 16);
-}
+size_t ransac_scratch_bytes(int num_jobs) { return ransac_scratch_bytes(num_jobs, sizeof(FundSlot)); }
 
 __global__ __launch_bounds__(256) void
 ransac_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_iterations, double thr2, uint64_t seed,
-    RansacSlot *__restrict__ slots, int32_t *__restrict__ done, int prefilter, unsigned long long *check)
+    FundSlot *__restrict__ slots, int32_t *__restrict__ done, int prefilter, unsigned long long *check)
 {
     __shared__ double4 mpt[kChunk];           // (x1, y1, x2, y2) of the staged matches, widened once
     __shared__ float4 mpf[kChunk];            // the same as the floats they are (pre-classification)
     __shared__ int s_wide;                    // a staged coordinate lies outside [-1, 1]
-    __shared__ int s_count[256], s_iter[256];
-    __shared__ double s_F[9];
-    __shared__ int s_wave[4], s_run, s_last;
+    __shared__ RansacLds<9> lds;
 
     const int jid = blockIdx.x / kRansacSplit, part = blockIdx.x % kRansacSplit;
     const RansacJob job = jobs[jid];
@@ -272,15 +264,13 @@ ransac_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_iteratio
         return;
     }
     // this part's iterations: whole passes of 256 * kHyp
-    const int per_part = ((max_iterations + kRansacSplit - 1) / kRansacSplit + 256 * kHyp - 1) / (256 * kHyp) * (256 * kHyp);
-    const int it_begin = part * per_part, it_end = min(max_iterations, it_begin + per_part);
-    const double thr_lo = thr2 * (1.0 - 1.7763568394002505e-15);     // 2^-49
-    const double thr_hi = thr2 * (1.0 + 1.7763568394002505e-15);
+    const RansacRange its = ransac_part_range(max_iterations, part, 256 * kHyp);
+    const RansacBand band(thr2);
     int best_count = 0, best_iter = 0x7fffffff;
     double bestF[9];
     for (int i = 0; i < 9; ++i) bestF[i] = 0.0;
 
-    for (int base = it_begin; base < it_end; base += 256 * kHyp) {
+    for (int base = its.begin; base < its.end; base += 256 * kHyp) {
         double F[kHyp][9];
         bool valid[kHyp];
         int cnt[kHyp];
@@ -289,7 +279,7 @@ ransac_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_iteratio
             const int it = base + h * 256 + tid;
             valid[h] = false; cnt[h] = 0;
             for (int i = 0; i < 9; ++i) F[h][i] = 0.0;
-            if (it >= it_end) continue;
+            if (it >= its.end) continue;
             // 8 distinct match ids, ascending (std::set order, :69-76)
             int idx[8], n = 0;
             for (uint64_t d = 0; n < 8; ++d) {
@@ -306,9 +296,9 @@ ransac_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_iteratio
             }
             double p1[8][2], p2[8][2];
             for (int i = 0; i < 8; ++i) {
-                const int a = job.corr[2 * idx[i]], b = job.corr[2 * idx[i] + 1];
-                p1[i][0] = job.pos1[2 * a]; p1[i][1] = job.pos1[2 * a + 1];
-                p2[i][0] = job.pos2[2 * b]; p2[i][1] = job.pos2[2 * b + 1];
+                const double4 m = load_match(job, idx[i]);
+                p1[i][0] = m.x; p1[i][1] = m.y;
+                p2[i][0] = m.z; p2[i][1] = m.w;
             }
             valid[h] = eight_point(p1, p2, F[h]);
         }
@@ -338,7 +328,7 @@ ransac_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_iteratio
                     // no divergence inside the loop
 #pragma unroll
                     for (int h = 0; h < kHyp; ++h)
-                        cnt[h] += sampson_below(F[h], m.x, m.y, m.z, m.w, thr2, thr_lo, thr_hi) ? 1 : 0;
+                        cnt[h] += sampson_below(F[h], m.x, m.y, m.z, m.w, band) ? 1 : 0;
                 }
                 continue;
             }
@@ -354,15 +344,15 @@ ransac_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_iteratio
                 const unsigned und = ~(r | (r >> 2)) & vmask;
                 if (und) {
                     const double4 m = mpt[i];
-                    if (und & 1u) cnt[0] += sampson_below(F[0], m.x, m.y, m.z, m.w, thr2, thr_lo, thr_hi) ? 1 : 0;
-                    if (und & 2u) cnt[1] += sampson_below(F[1], m.x, m.y, m.z, m.w, thr2, thr_lo, thr_hi) ? 1 : 0;
+                    if (und & 1u) cnt[0] += sampson_below(F[0], m.x, m.y, m.z, m.w, band) ? 1 : 0;
+                    if (und & 2u) cnt[1] += sampson_below(F[1], m.x, m.y, m.z, m.w, band) ? 1 : 0;
                 }
                 if (check) {
                     // self-check: every decision the floats took against the double path
                     const double4 m = mpt[i];
 #pragma unroll
                     for (int h = 0; h < kHyp; ++h) {
-                        const bool ref = sampson_below(F[h], m.x, m.y, m.z, m.w, thr2, thr_lo, thr_hi);
+                        const bool ref = sampson_below(F[h], m.x, m.y, m.z, m.w, band);
                         const bool in = (r >> h) & 1u, out = (r >> (2 + h)) & 1u;
                         if (valid[h] && ((in && !ref) || (out && ref) || (in && out))) atomicAdd(&check[0], 1ull);
                         if (valid[h] && !in && !out) atomicAdd(&check[1], 1ull);
@@ -380,79 +370,25 @@ ransac_kernel(const RansacJob *__restrict__ jobs, int num_jobs, int max_iteratio
 #pragma unroll
         for (int h = 0; h < kHyp; ++h) {
             const int it = base + h * 256 + tid;
-            // strictly more inliers wins; equal counts keep the earlier iteration (:47)
-            if (valid[h] && (cnt[h] > best_count || (cnt[h] == best_count && cnt[h] > 0 && it < best_iter))) {
+            if (valid[h] && ransac_better(cnt[h], it, best_count, best_iter)) {
                 best_count = cnt[h]; best_iter = it;
                 for (int i = 0; i < 9; ++i) bestF[i] = F[h][i];
             }
         }
     }
-    // block argmax: (count desc, iteration asc)
-    s_count[tid] = best_count; s_iter[tid] = best_iter;
-    __syncthreads();
-    for (int st = 128; st >= 1; st >>= 1) {
-        if (tid < st) {
-            const int c2 = s_count[tid + st], i2 = s_iter[tid + st];
-            if (c2 > s_count[tid] || (c2 == s_count[tid] && i2 < s_iter[tid])) { s_count[tid] = c2; s_iter[tid] = i2; }
-        }
-        __syncthreads();
-    }
-    int win_count = s_count[0], win_iter = s_iter[0];
-    if (best_count == win_count && best_iter == win_iter && win_count > 0)
-        for (int i = 0; i < 9; ++i) s_F[i] = bestF[i];
-    __syncthreads();
-    // this part's best into its slot; the last part to get here goes on with all of them
-    if (tid == 0) {
-        RansacSlot &mine = slots[(size_t)jid * kRansacSplit + part];
-        mine.count = win_count; mine.iter = win_iter;
-        for (int i = 0; i < 9; ++i) mine.F[i] = win_count > 0 ? s_F[i] : 0.0;
-        __threadfence();
-        s_last = atomicAdd(&done[jid], 1) == kRansacSplit - 1;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    if (tid == 0) {
-        __threadfence();
-        int bc = 0, bi = 0x7fffffff, bp = -1;
-        for (int p = 0; p < kRansacSplit; ++p) {
-            const RansacSlot &sl = slots[(size_t)jid * kRansacSplit + p];
-            // strictly more inliers wins; equal counts keep the earlier iteration (:47)
-            if (sl.count > bc || (sl.count == bc && sl.count > 0 && sl.iter < bi)) { bc = sl.count; bi = sl.iter; bp = p; }
-        }
-        s_count[0] = bc; s_iter[0] = bi;
-        if (bp >= 0) for (int i = 0; i < 9; ++i) s_F[i] = slots[(size_t)jid * kRansacSplit + bp].F[i];
-        done[jid] = 0;                 // ready for the next launch
-        s_run = 0;
-    }
-    __syncthreads();
-    win_count = s_count[0]; win_iter = s_iter[0];
+    int win_count, win_iter;
+    double Fw[9];
+    if (!ransac_elect(lds, slots, done, jid, part, tid, best_count, best_iter, bestF, win_count, win_iter, Fw)) return;
     if (win_count == 0) {
-        if (tid == 0) { *job.count_out = 0; if (job.F_out) for (int i = 0; i < 9; ++i) job.F_out[i] = 0.0; }
+        if (tid == 0) ransac_no_winner(job);
         return;
     }
-    double Fw[9];
-    for (int i = 0; i < 9; ++i) Fw[i] = s_F[i];
     if (tid == 0 && job.F_out) for (int i = 0; i < 9; ++i) job.F_out[i] = Fw[i];
-    // ordered list of the inlier ids of the winning hypothesis
-    const int lane = tid & 63, wave = tid >> 6;
-    for (int c0 = 0; c0 < k; c0 += 256) {
-        const int i = c0 + tid;
-        bool in = false;
-        if (i < k) {
-            const int a = job.corr[2 * i], b = job.corr[2 * i + 1];
-            in = sampson(Fw, job.pos1[2 * a], job.pos1[2 * a + 1], job.pos2[2 * b], job.pos2[2 * b + 1]) < thr2;
-        }
-        const unsigned long long bal = __ballot(in);
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int off = s_run;
-        for (int w = 0; w < wave; ++w) off += s_wave[w];
-        if (in) job.inliers_out[off + __popcll(bal & ((1ull << lane) - 1ull))] = i;
-        __syncthreads();
-        if (tid == 0) s_run += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
-    }
-    if (tid == 0) *job.count_out = s_run;
+    // ordered list of the inlier ids of the winning hypothesis, by the reference's own test
+    ransac_list_inliers(lds, job, tid, [&](int i) {
+        const double4 m = load_match(job, i);
+        return sampson(Fw, m.x, m.y, m.z, m.w) < thr2;
+    });
 }
 
 // Scoring mode of the process and, per device, the counters of mode 2 (every pre-classified decision compared with
@@ -479,9 +415,8 @@ void launch_ransac(const RansacJob *d_jobs, int num_jobs, int max_iterations, do
     uint64_t seed, void *scratch, hipStream_t s)
 {
     if (num_jobs <= 0) return;
-    RansacSlot *slots = static_cast<RansacSlot *>(scratch);
-    int32_t *done = reinterpret_cast<int32_t *>(static_cast<char *>(scratch) + (size_t)num_jobs * kRansacSplit * sizeof(RansacSlot));
-    (void)hipMemsetAsync(done, 0, (size_t)num_jobs * sizeof(int32_t), s);
+    FundSlot *slots = static_cast<FundSlot *>(scratch);
+    int32_t *done = ransac_scratch_done(scratch, num_jobs, sizeof(FundSlot), s);
     const int mode = g_ransac_mode.load();
     hipLaunchKernelGGL(ransac_kernel, dim3(num_jobs * kRansacSplit), dim3(256), 0, s, d_jobs, num_jobs, max_iterations,
         threshold * threshold, seed, slots, done, mode != 0 ? 1 : 0, mode == 2 ? ransac_check_block(true) : nullptr);
