@@ -550,9 +550,21 @@ static double now_ms(void)
  * TrustRegionMinimizer + LevenbergMarquardtStrategy + Schur elimination of
  * the point blocks + dense Cholesky of the reduced camera system.
  */
-ORACLE_API int
-oracle_ba_solve(const ba_problem *p, const ba_options *o, ba_summary *sum)
+/* One row of the per-iteration trace (oracle_ba_solve_trace): what the iteration went in with, what its step gave
+ * and what became of it.  A row is opened at the head of the loop, before FinalizeIterationAndCheckIfMinimizerCanContinue:
+ * a solve that ends there leaves a last row with outcome TR_HEAD_STOP and NaN in the step's fields. */
+enum { TR_RADIUS = 0, TR_X_COST, TR_X_NORM, TR_GRAD_MAX, TR_LAST_SUCCESSFUL, TR_MODEL_COST_CHANGE, TR_CAND_COST,
+       TR_STEP_NORM, TR_RELATIVE_DECREASE, TR_OUTCOME, TR_SOLVE, TR_INVALID_STEPS, TR_FIELDS };
+enum { TR_HEAD_STOP = -1, TR_ACCEPTED = 0, TR_REJECTED = 1, TR_INVALID = 2, TR_PARAMETER_STOP = 3, TR_FUNCTION_STOP = 4,
+       TR_FAILURE_STOP = 5 };
+/* TR_SOLVE: 1 solved, 0 a point block V_j + D^2 was not positive definite, -1 the reduced system's Cholesky failed,
+ * -2 the step was not finite */
+
+static int
+ba_solve_impl(const ba_problem *p, const ba_options *o, ba_summary *sum, double *trace, int trace_cap, int *trace_rows)
 {
+    double *row = NULL;
+    int rows = 0;
     ba_layout L;
     layout_build(p, o, &L);
     const int C = L.C, M = L.M, O = L.O, nc = L.ncam, np = L.pdim * M;
@@ -654,10 +666,18 @@ oracle_ba_solve(const ba_problem *p, const ba_options *o, ba_summary *sum)
     X_NORM();
     EVAL_GRADIENT(1);
     sum->initial_cost = x_cost;
+    /* TrustRegionMinimizer::Init: a cost that is not finite fails the first evaluation (iteration 0) */
+    if (!isfinite(x_cost)) { term = T_FAILURE; goto done; }
     if (grad_max <= o->gradient_tolerance) { term = T_GRADIENT; goto done; }
 
     int last_successful = 0;
     for (;;) {
+        if (trace && rows < trace_cap) {
+            row = trace + (size_t)TR_FIELDS * rows++;
+            for (int i = 0; i < TR_FIELDS; ++i) row[i] = NAN;
+            row[TR_RADIUS] = radius; row[TR_X_COST] = x_cost; row[TR_X_NORM] = x_norm; row[TR_GRAD_MAX] = grad_max;
+            row[TR_LAST_SUCCESSFUL] = last_successful; row[TR_OUTCOME] = TR_HEAD_STOP; row[TR_INVALID_STEPS] = invalid_steps;
+        } else row = NULL;
         /* FinalizeIterationAndCheckIfMinimizerCanContinue: max iterations,
          * then gradient tolerance (after a successful step), then radius */
         if (iteration >= o->max_num_iterations) { term = T_NO_CONV; break; }
@@ -709,7 +729,7 @@ oracle_ba_solve(const ba_problem *p, const ba_options *o, ba_summary *sum)
                 }
                 for (int a = 0; a < 3; ++a) V[a][a] += diag_p[3 * j + a] / radius;
                 double Vi[3][3];
-                if (k1 > k0 && !inv3_spd(V, Vi)) { solve_ok = 0; break; }
+                if (k1 > k0 && !inv3_spd(V, Vi)) { solve_ok = 0; break; }   /* (TR_SOLVE 0) */
                 if (k1 == k0) { memset(Vi, 0, sizeof Vi); for (int a = 0; a < 3; ++a) Vi[a][a] = 1.0 / V[a][a]; }
                 memcpy(Vinv + 9 * j, Vi, sizeof Vi);
                 ge[3 * j] = g[0]; ge[3 * j + 1] = g[1]; ge[3 * j + 2] = g[2];
@@ -737,9 +757,11 @@ oracle_ba_solve(const ba_problem *p, const ba_options *o, ba_summary *sum)
                 }
             }
         }
+        int solve_code = solve_ok;
         if (solve_ok && nc > 0) {
             memcpy(step_c, rhs, sizeof(double) * nc);
             solve_ok = cholesky_solve(S, nc, step_c);
+            if (!solve_ok) solve_code = -1;
         }
         if (solve_ok && L.pdim) {
             /* back substitution: y_p = Vi (g - sum_k W_k^T y_c) */
@@ -763,7 +785,9 @@ oracle_ba_solve(const ba_problem *p, const ba_options *o, ba_summary *sum)
             for (int i = 0; i < nc && finite; ++i) finite = isfinite(step_c[i]);
             for (int i = 0; i < np && finite; ++i) finite = isfinite(step_p[i]);
             solve_ok = finite;
+            if (!finite) solve_code = -2;
         }
+        if (row) row[TR_SOLVE] = solve_code;
         reuse_diagonal = 1;
         if (solve_ok) {
             /* the solver returns y with J y ~ r; the step is -y */
@@ -781,10 +805,12 @@ oracle_ba_solve(const ba_problem *p, const ba_options *o, ba_summary *sum)
             }
             model_cost_change = mcc;
             step_valid = model_cost_change > 0.0;
+            if (row) row[TR_MODEL_COST_CHANGE] = mcc;
         }
         if (!step_valid) {
             /* HandleInvalidStep */
-            if (++invalid_steps >= o->max_consecutive_invalid_steps) { term = T_FAILURE; break; }
+            if (row) row[TR_OUTCOME] = TR_INVALID;
+            if (++invalid_steps >= o->max_consecutive_invalid_steps) { if (row) row[TR_OUTCOME] = TR_FAILURE_STOP; term = T_FAILURE; break; }
             radius = radius / decrease_factor; decrease_factor *= 2.0; reuse_diagonal = 1;
             sum->num_unsuccessful_steps++;
             continue;
@@ -802,12 +828,14 @@ oracle_ba_solve(const ba_problem *p, const ba_options *o, ba_summary *sum)
         for (int c = 0; c < C; ++c) FOR_ACTIVE_CAM_SLOTS(c, { const double d_ = cams[7 * c + slot] - cams_c[7 * c + slot]; sn += d_ * d_; })
         if (L.pdim) for (int i = 0; i < 4 * M; ++i) { const double d_ = pts[i] - pts_c[i]; sn += d_ * d_; }
         const double step_norm = sqrt(sn);
-        if (step_norm <= o->parameter_tolerance * (x_norm + o->parameter_tolerance)) { term = T_PARAMETER; break; }
+        if (row) { row[TR_CAND_COST] = cand_cost; row[TR_STEP_NORM] = step_norm; }
+        if (step_norm <= o->parameter_tolerance * (x_norm + o->parameter_tolerance)) { if (row) row[TR_OUTCOME] = TR_PARAMETER_STOP; term = T_PARAMETER; break; }
         /* FunctionToleranceReached */
         const double cost_change = x_cost - cand_cost;
-        if (fabs(cost_change) <= o->function_tolerance * x_cost) { term = T_FUNCTION; break; }
+        if (fabs(cost_change) <= o->function_tolerance * x_cost) { if (row) row[TR_OUTCOME] = TR_FUNCTION_STOP; term = T_FUNCTION; break; }
 
         const double relative_decrease = cost_change / model_cost_change;
+        if (row) { row[TR_RELATIVE_DECREASE] = relative_decrease; row[TR_OUTCOME] = relative_decrease > o->min_relative_decrease ? TR_ACCEPTED : TR_REJECTED; }
         if (relative_decrease > o->min_relative_decrease) {
             /* HandleSuccessfulStep */
             memcpy(cams, cams_c, sizeof(double) * 7 * C);
@@ -848,7 +876,22 @@ done:
     free(scale_c); free(scale_p); free(diag_c); free(diag_p); free(gc); free(gp);
     free(S); free(rhs); free(step_c); free(step_p); free(dc); free(dp); free(Vinv); free(ge);
     layout_free(&L);
+    if (trace_rows) *trace_rows = rows;
     return 0;
+}
+
+ORACLE_API int
+oracle_ba_solve(const ba_problem *p, const ba_options *o, ba_summary *sum)
+{
+    return ba_solve_impl(p, o, sum, NULL, 0, NULL);
+}
+
+/* The same solve, with a row of TR_FIELDS doubles per iteration in trace (room for trace_cap rows; a solve of n
+ * iterations opens at most n + 1) and the number of rows opened in *trace_rows. */
+ORACLE_API int
+oracle_ba_solve_trace(const ba_problem *p, const ba_options *o, ba_summary *sum, double *trace, int trace_cap, int *trace_rows)
+{
+    return ba_solve_impl(p, o, sum, trace, trace_cap, trace_rows);
 }
 
 /* ------------------------------------------------------------------ */

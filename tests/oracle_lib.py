@@ -346,6 +346,35 @@ def oracle_ba_solve(scene, **opt_kw):
     return s
 
 
+TRACE_FIELDS = ("radius", "x_cost", "x_norm", "grad_max", "last_successful", "model_cost_change", "cand_cost", "step_norm",
+                "relative_decrease", "outcome", "solve", "invalid_steps")
+# trace["outcome"]: what became of the iteration (TR_* of oracle/ba_oracle.c)
+TR_HEAD_STOP, TR_ACCEPTED, TR_REJECTED, TR_INVALID, TR_PARAMETER_STOP, TR_FUNCTION_STOP, TR_FAILURE_STOP = -1, 0, 1, 2, 3, 4, 5
+# trace["solve"]: 1 solved, 0 a point block was not positive definite, -1 the reduced system's Cholesky failed, -2 not finite
+TR_SOLVED, TR_POINT_BLOCK_FAILED, TR_CHOLESKY_FAILED, TR_STEP_NOT_FINITE = 1, 0, -1, -2
+
+
+def oracle_ba_solve_trace(scene, **opt_kw):
+    """oracle_ba_solve (in place on the scene) with its per-iteration trace: (summary, dict of TRACE_FIELDS -> array of
+    one value per row).  A row is opened at the head of every pass of the loop, so a solve that ends in the checks
+    there (max iterations, gradient after a step, radius) leaves a last row with outcome TR_HEAD_STOP whose step
+    fields are NaN; a solve that ended before the loop (gradient or a non-finite cost at the start) has no rows."""
+    lib = oracle()
+    p = ba_problem_struct(scene)
+    o = ba_default_options(**opt_kw)
+    s = OBaSummary()
+    cap = max(int(o.max_num_iterations), 0) + 2
+    buf = np.zeros(cap * len(TRACE_FIELDS))
+    rows = C.c_int(0)
+    fn = lib.oracle_ba_solve_trace
+    fn.argtypes = [C.POINTER(OBaProblem), C.POINTER(OBaOptions), C.POINTER(OBaSummary), _f64p, C.c_int, C.POINTER(C.c_int)]
+    fn.restype = C.c_int
+    rc = fn(C.byref(p), C.byref(o), C.byref(s), buf, cap, C.byref(rows))
+    assert rc == 0 and rows.value < cap
+    t = buf.reshape(cap, len(TRACE_FIELDS))[:rows.value]
+    return s, {name: t[:, i].copy() for i, name in enumerate(TRACE_FIELDS)}
+
+
 def oracle_ba_residuals(scene):
     lib = oracle()
     p = ba_problem_struct(scene)
