@@ -756,6 +756,74 @@ OSFM_API int osfm_scene_tk_align(osfm_scene *s, int n, const int32_t *views, con
     int32_t *num_tracks);
 
 
+/* ---- placing one view against the scene's points: RANSAC over affine cameras (resection) ----
+ *
+ * The camera model is linear in the point: u = x.p / s - o_x, v = y.p / s - o_y in the normalised coordinates
+ * u = -2 (px / W - 0.5), v = -2 (py / H - 0.5), so a view that sees N triangulated points is an affine camera
+ * (u, v) = A X + (c, d) that four non-coplanar points fix.  Hypotheses from four-point samples (the sampler of the
+ * entries above under (seed, stream_id, iteration, draw)), every hypothesis scored against all N points, the winner
+ * refitted over its inliers and projected onto the camera model.  No mirror ambiguity (the points carry their
+ * depth), no baseline enters, and no all-point fallback.  The reference has no such step; what is computed, in
+ * full: INTEGRATION.md section 3b. */
+typedef struct osfm_resect_options {
+    int32_t max_iterations;     /* 0      0: floor(log(1 - probability) / log(1 - inlier_ratio^4)) = 107, held to 1 .. 2^20;
+                                 *        at most 2^20 may be asked for */
+    int32_t min_consensus;      /* 8      inliers outside the sample that must support a hypothesis */
+    double probability;         /* 0.999 */
+    double inlier_ratio;        /* 0.5 */
+    double max_error_px;        /* 3.0    a point is an inlier iff its error is BELOW this (osfm_tk_options' value) */
+    double min_pivot;           /* 1e-6   a sample is unusable when a pivot of its 3 x 3 elimination is below this times the
+                                 *        largest entry of the matrix (coplanar or repeated points); the refit is refused when a
+                                 *        pivot of its covariance is below this times the largest diagonal entry.  1e-6 keeps
+                                 *        the rounding of either solve near 1e-10 and is far below what any sample that can
+                                 *        gather support has */
+    double min_axis_ratio;      /* 0.5    sigma_2 / sigma_1 of the hypothesis' 2 x 3 matrix below this: not a scaled-orthographic view */
+    int32_t estimate_scale;     /* 0      != 0: scale = 2 / (sigma_1 + sigma_2) of the refitted matrix; 0: `scale` */
+    int32_t device;             /* 0 */
+    double scale;               /* 1.0    the camera's scale when it is not estimated (the reference's cameras: 1, fixed) */
+    uint64_t seed;              /* 0      stream seed of the counter-based sampler */
+} osfm_resect_options;
+OSFM_API int osfm_resect_options_default(osfm_resect_options *opts);
+/* points per scoring workgroup (the unit of the fixed-order sums) and hypotheses per staged chunk, as built
+ * (either may be NULL) */
+OSFM_API int osfm_resect_limits(int32_t *tile, int32_t *chunk);
+
+enum {
+    OSFM_RESECT_OK = 0,         /* a supported hypothesis won */
+    OSFM_RESECT_TOO_FEW = 1,    /* n < 4 + min_consensus: nothing is launched */
+    OSFM_RESECT_NO_MODEL = 2    /* no supported hypothesis: identity, scale opts.scale, zero offsets, no inliers */
+};
+
+typedef struct osfm_resect_result {
+    int32_t status;             /* OSFM_RESECT_* */
+    int32_t iterations;         /* hypotheses drawn */
+    int32_t usable_models;      /* ... whose sample passes the pivot and axis-ratio tests */
+    int32_t supported_models;   /* ... and have min_consensus inliers outside the sample */
+    int32_t best_iteration;     /* the winner's iteration, -1 without one */
+    int32_t ransac_inliers;     /* the winner's inliers under its own hypothesis (consensus + 4) */
+    int32_t num_inliers;        /* inliers of the final camera */
+    int32_t refit_used;         /* 1: the final camera comes from the refit over the winner's inliers; 0: from the winner */
+    double mean_error_px;       /* mean error of the final camera's inliers */
+    double score_kernel_ms;     /* device time of the scoring kernel (all hypotheses x all points) */
+} osfm_resect_result;
+
+/* points [n][3]: the points' positions; xy [n][2]: their pixel positions in the view (img_width x img_height).
+ * rotation [9]: row-major local -> world (columns x, y, z axis, as osfm_tk_align's bases); *scale; offsets [2];
+ * inlier [n] (may be NULL): the final camera's inliers.  opts NULL: the defaults.  stream_id: the sampler's stream
+ * (osfm_tk_align's group_id). */
+OSFM_API int osfm_resect_view(const double *points, const double *xy, int32_t n, int32_t img_width, int32_t img_height,
+    const osfm_resect_options *opts, uint64_t stream_id, double *rotation, double *scale, double *offsets, uint8_t *inlier,
+    osfm_resect_result *result);
+/* osfm_resect_view on the scene's table: the live features of `view` (feature and track alive) whose track has a
+ * point, in ascending feature order, X = point.xyz / point.w; selected and gathered on the device.  The view needs
+ * no camera and the scene is not changed: the caller hands the result to osfm_scene_align_views.  *num_points (may
+ * be NULL): how many correspondences that were; inlier (may be NULL) has capacity inlier_capacity and is written
+ * for min(*num_points, inlier_capacity) of them. */
+OSFM_API int osfm_scene_resect_view(osfm_scene *s, int32_t view, const osfm_resect_options *opts, uint64_t stream_id,
+    double *rotation, double *scale, double *offsets, uint8_t *inlier, int32_t inlier_capacity, osfm_resect_result *result,
+    int32_t *num_points);
+
+
 /* The device part of orthosfm::filterTracksWithReprojectionError
  * (outlier_filtering.cpp:127-192).  p holds the FULL-SIZE tracks (the
  * caller's filterTracksToAvailableCameras(cameras, tracks, true, true)

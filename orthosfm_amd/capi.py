@@ -156,6 +156,25 @@ class TkResult(C.Structure):
 
 TK_RANSAC, TK_FALLBACK, TK_TOO_FEW, TK_DEGENERATE = 0, 1, 2, 3
 
+
+class ResectOptions(C.Structure):
+    """osfm_resect_options"""
+    _fields_ = [("max_iterations", C.c_int32), ("min_consensus", C.c_int32), ("probability", C.c_double),
+                ("inlier_ratio", C.c_double), ("max_error_px", C.c_double), ("min_pivot", C.c_double),
+                ("min_axis_ratio", C.c_double), ("estimate_scale", C.c_int32), ("device", C.c_int32),
+                ("scale", C.c_double), ("seed", C.c_uint64)]
+
+
+class ResectResult(C.Structure):
+    """osfm_resect_result"""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("usable_models", C.c_int32),
+                ("supported_models", C.c_int32), ("best_iteration", C.c_int32), ("ransac_inliers", C.c_int32),
+                ("num_inliers", C.c_int32), ("refit_used", C.c_int32), ("mean_error_px", C.c_double),
+                ("score_kernel_ms", C.c_double)]
+
+
+RESECT_OK, RESECT_TOO_FEW, RESECT_NO_MODEL = 0, 1, 2
+
 SIFT_MAX_OCTAVES = 16
 
 
@@ -264,6 +283,7 @@ EXPORTS = [
     "osfm_scene_triangulate", "osfm_scene_filter_reprojection", "osfm_scene_local_adjustment", "osfm_scene_global_adjustment",
     "osfm_scene_filter_outliers", "osfm_scene_download",
     "osfm_tk_options_default", "osfm_tk_align", "osfm_tk_resolve_ambiguity", "osfm_scene_tk_align",
+    "osfm_resect_options_default", "osfm_resect_limits", "osfm_resect_view", "osfm_scene_resect_view",
     "osfm_tracks_compute", "osfm_tracks_compute_ranges", "osfm_build_groups",
     "osfm_tracks_builder_create", "osfm_tracks_builder_feed", "osfm_tracks_builder_finish", "osfm_tracks_builder_destroy",
     "osfm_tracks_select_observations",
@@ -334,6 +354,11 @@ lib.osfm_match_debug_view_bank.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINT
 lib.osfm_match_debug_set_view_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                  C.c_void_p, C.c_void_p]
 lib.osfm_ba_small_limits.argtypes = [C.POINTER(C.c_int32)] * 3
+lib.osfm_resect_limits.argtypes = [C.POINTER(C.c_int32)] * 2
+lib.osfm_resect_view.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.osfm_scene_resect_view.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
 lib.osfm_ba_debug_cholesky_solve.restype = C.c_int
 lib.osfm_ba_debug_cholesky_solve.argtypes = [C.c_int, C.c_int, _f64p, _f64p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, _f64p, _i32p, _i32p]

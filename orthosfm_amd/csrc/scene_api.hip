@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "ba_solve.h"
+#include "resect_kernels.h"
 #include "tk_kernels.h"
 
 using namespace osfm;
@@ -1057,6 +1058,67 @@ int osfm_scene_tk_align(osfm_scene *sc, int n, const int32_t *views, const osfm_
     }
     return tk_align_core(d_rows.as<double>(), N, n, W, H, o, iterations, group_id, s, sg.ev[0].a, sg.ev[0].b, basis_1, basis_2,
         offsets, inlier, inlier ? inlier_capacity : 0, result);
+}
+
+namespace {
+
+// the selected features of one view with their tracks' points as the resection's correspondences: data [5][N],
+// rows X, Y, Z, u, v, column = the feature's rank among the selected ones
+__global__ void scene_resect_gather_kernel(int64_t F, int N, int W, int H, const int32_t *__restrict__ sel,
+    const int32_t *__restrict__ scan, const int32_t *__restrict__ track_of, const double *__restrict__ point,
+    const double2 *__restrict__ xy, double *__restrict__ data)
+{
+    const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= F || !sel[f]) return;
+    const int j = scan[f];
+    if (j < 0 || j >= N) return;
+    const double *P = point + 4 * (size_t)track_of[f];
+    const double2 p = xy[f];
+    data[j] = P[0] / P[3];
+    data[(size_t)N + j] = P[1] / P[3];
+    data[2 * (size_t)N + j] = P[2] / P[3];
+    data[3 * (size_t)N + j] = tk_normalise(p.x, W);
+    data[4 * (size_t)N + j] = tk_normalise(p.y, H);
+}
+
+}  // namespace
+
+int osfm_scene_resect_view(osfm_scene *sc, int32_t view, const osfm_resect_options *opts, uint64_t stream_id, double *rotation,
+    double *scale, double *offsets, uint8_t *inlier, int32_t inlier_capacity, osfm_resect_result *result, int32_t *num_points)
+{
+    if (!sc || !rotation || !scale || !offsets || !result || (inlier && inlier_capacity < 0)) {
+        set_error("scene_resect_view: bad arguments"); return OSFM_E_ARG;
+    }
+    osfm_resect_options o;
+    int iterations = 0;
+    OSFM_RETURN_IF(resect_check_options(opts, &o, &iterations));
+    OSFM_RETURN_IF(check_views(sc, &view, 1, "scene_resect_view"));
+    const int W = sc->img_w[view], H = sc->img_h[view];
+    std::lock_guard<std::mutex> lock(sc->mu);
+    OSFM_RETURN_IF(select_device(sc->device));
+    StreamLease sg;
+    OSFM_RETURN_IF(sg.acquire());
+    hipStream_t s = sg.s;
+    const int64_t F = sc->F;
+    int32_t *sel = sc->sel.as<int32_t>(), *scan = sc->scan.as<int32_t>();
+    DevArray d_views, d_data;
+    OSFM_RETURN_IF(set_cam_map(sc, &view, 1, s, &d_views));
+    // the live features of the view whose track has a point (has_point as the selection's track mask), ranked by a scan
+    hipLaunchKernelGGL(scene_select_kernel, dim3(blocks_for(F + 1)), dim3(kThreads), 0, s, F, sc->feat_view.as<int32_t>(),
+        sc->track_of.as<int32_t>(), sc->alive_f.as<uint8_t>(), sc->alive_t.as<uint8_t>(), sc->cam_map.as<int32_t>(),
+        sc->has_point.as<uint8_t>(), sel);
+    OSFM_RETURN_IF(exclusive_scan(sc, sel, scan, F + 1, s));
+    OSFM_HIP_CHECK(hipGetLastError());
+    int N = 0;
+    OSFM_RETURN_IF(read_total(scan, F, s, &N));
+    if (num_points) *num_points = N;
+    if (!resect_too_few(N, o)) {
+        OSFM_RETURN_IF(d_data.alloc((size_t)N * 5 * 8));
+        hipLaunchKernelGGL(scene_resect_gather_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, s, F, N, W, H, sel, scan,
+            sc->track_of.as<int32_t>(), sc->point.as<double>(), sc->feat_xy.as<double2>(), d_data.as<double>());
+    }
+    return resect_core(d_data.as<double>(), N, W, H, o, iterations, stream_id, s, sg.ev[0].a, sg.ev[0].b, rotation, scale, offsets,
+        inlier, inlier ? inlier_capacity : 0, result);
 }
 
 int osfm_scene_filter_outliers(osfm_scene *sc, osfm_outlier_stats *stats, int32_t *num_killed)

@@ -351,6 +351,7 @@ class Timings:
     pose_host_s: float = 0.0
     pose_s: float = 0.0
     total_s: float = 0.0
+    resected_groups: int = 0      # camera groups started from a resection against the scene's points (weak_group="resect")
 
 
 @dataclass
@@ -381,6 +382,7 @@ class Result:
     pair_status: np.ndarray | None = None
     initial_alignments: list = field(default_factory=list)      # one tk.Alignment per group (initial_alignment="tk")
     verification: str = "none"       # model of the geometric verification: "none", "fundamental" or "affine"
+    resected_groups: list = field(default_factory=list)         # ordinals of the groups started from a resection
 
 
 def _problem(model, cams, const, width, height, points, xy, obs_cam, obs_pt):
@@ -712,10 +714,26 @@ def join_background():
         _background.pop().join()
 
 
+WEAK_GROUP_POLICIES = ("raise", "resect")
+
+
+def weak_group_action(tk_status, first_group, policy):
+    """What a camera group does with the status of its Tomasi-Kanade alignment: "tk" (start from the model the
+    alignment returned: a supported one, or the fallback's), "resect" (place its new views against the scene's points)
+    or "raise" (too few tracks: the job ends, as the reference throws).  A group is weak when no supported model won
+    (FALLBACK, TOO_FEW, DEGENERATE); the first group has no points to resect against."""
+    if policy not in WEAK_GROUP_POLICIES:
+        raise ValueError(f"weak_group {policy!r}: 'raise' or 'resect'")
+    weak = tk_status in (capi.TK_FALLBACK, capi.TK_TOO_FEW, capi.TK_DEGENERATE)
+    if weak and policy == "resect" and not first_group:
+        return "resect"
+    return "raise" if tk_status == capi.TK_TOO_FEW else "tk"
+
+
 def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2.0, off_perturb=0.01,
                         seed=7, timings=None, capture=(), max_groups=None, verbose=False, view_ids=None,
                         euler_dof=4, check_incremental=False, use_scene=True, initial_alignment="perturbed",
-                        alignments=None, local_solver="general"):
+                        alignments=None, local_solver="general", weak_group="raise", tk_options=None, resected=None):
     """runPoseEstimation (reconstruct.cpp:174-295) on the track table.  initial_alignment: "perturbed" or "tk" (see
     the module docstring); with "tk", group_id is the group's ordinal, seed the sampler's seed, and the groups'
     tk.Alignment records are appended to `alignments` (a list, if given).  use_scene: the table lives on the device
@@ -723,9 +741,16 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
     tracks on the host and goes through the per-call entries of the C ABI (what a caller without the scene does;
     the two forms produce the same cameras, flags and points to the bit: tests/test_e2e_gpu.py).  local_solver:
     "general", or "small": every camera group's local adjustment in the one-workgroup form (small_form=2 on its
-    options; the global adjustments keep the general form)."""
+    options; the global adjustments keep the general form).  tk_options: a dict of tk.options() values for the
+    alignment (over seed and device).  weak_group: "raise", or "resect": a group after the first whose alignment ends
+    without a supported model (weak_group_action) starts its aligned views from their global cameras and its new views
+    from a resection against the scene's points (resect.resect / Scene.resect_view, stream_id = the group's ordinal);
+    if a resection is not OK the group does what "raise" does.  The ordinals of the resected groups are appended to
+    `resected` (a list, if given) and counted in timings.resected_groups."""
     if local_solver not in ("general", "small"):
         raise ValueError(f"local_solver {local_solver!r}: 'general' or 'small'")
+    if weak_group not in WEAK_GROUP_POLICIES:
+        raise ValueError(f"weak_group {weak_group!r}: 'raise' or 'resect'")
     if initial_alignment not in ("perturbed", "tk"):
         raise ValueError(f"initial_alignment {initial_alignment!r}: 'perturbed' or 'tk'")
     use_tk = initial_alignment == "tk"
@@ -786,8 +811,10 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
         from . import tk as TK
         t0 = time.perf_counter()
         n = len(ids)
+        tk_opts = dict(seed=seed, device=device)
+        tk_opts.update(tk_options or {})
         if scene is not None:
-            al = scene.tk_align(ids, group_id=ordinal, seed=seed, device=device)
+            al = scene.tk_align(ids, group_id=ordinal, **tk_opts)
         else:
             # the live tracks all n views see, in ascending track order, cameras in the order of ids
             idx = tt.features_of_views(ids)
@@ -798,8 +825,20 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
             cam_of[ids] = np.arange(n, dtype=np.int32)
             xy = np.zeros((int(full.sum()), n, 2))
             xy[(np.cumsum(full) - 1)[run][full[run]], cam_of[tt.view[fi]]] = tt.xy[fi]
-            al = TK.align(xy, W, H, group_id=ordinal, seed=seed, device=device)
-        if al.status == capi.TK_TOO_FEW:
+            al = TK.align(xy, W, H, group_id=ordinal, **tk_opts)
+        action = weak_group_action(al.status, not aligned, weak_group)
+        if action == "resect":
+            lp = resect_start(ordinal, ids)
+            if lp is not None:
+                if alignments is not None:
+                    alignments.append(al)
+                tm.resected_groups += 1
+                if resected is not None:
+                    resected.append(ordinal)
+                tm.initial_alignment_s += time.perf_counter() - t0
+                return lp
+            action = weak_group_action(al.status, not aligned, "raise")
+        if action == "raise":
             raise RuntimeError(f"group {list(ids)}: too few tracks ({al.num_tracks}) for the Tomasi-Kanade alignment")
         has_global = [bool(is_aligned[v]) for v in ids]
         rot = np.array([_cam_rotation(model, cams[v]) if is_aligned[v] else np.eye(3) for v in ids])
@@ -808,6 +847,27 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
             alignments.append(al)
         lp = TK.bases_to_params(model, al.basis_1 if choice == 1 else al.basis_2)
         tm.initial_alignment_s += time.perf_counter() - t0
+        return lp
+
+    def resect_start(ordinal, ids):
+        """The group's aligned views from their global cameras, the others resected against the points of the tracks
+        they see (in the global frame); None when a resection is not OK."""
+        from . import resect as RS
+        lp = np.zeros((len(ids), 7))
+        for k, v in enumerate(ids):
+            if is_aligned[v]:
+                lp[k] = cams[v]
+                continue
+            if scene is not None:
+                pl = scene.resect_view(v, stream_id=ordinal, seed=seed, device=device)
+            else:
+                # the live features of the view whose track has a point, in ascending feature order
+                f = np.flatnonzero(tt.live_f & (tt.view == v) & tt.has_point[tt.track_of])
+                P4 = tt.point[tt.track_of[f]]
+                pl = RS.resect(P4[:, :3] / P4[:, 3:4], tt.xy[f], W, H, stream_id=ordinal, seed=seed, device=device)
+            if pl.status != capi.RESECT_OK:
+                return None
+            lp[k] = RS.placement_to_params(model, pl)
         return lp
 
     def solve(kind, prob, options):
@@ -1077,25 +1137,28 @@ def _global_ba(tt, model, cams, const, aligned, W, H, V, solve, kind, opt, tm):
 
 def reconstruct(iset, solver=0, matcher="exhaustive", device=0, verify=True, rot_perturb_deg=2.0,
                 off_perturb=0.01, seed=7, capture=(), max_groups=None, verbose=False,
-                check_incremental=False, use_scene=True, initial_alignment="perturbed", local_solver="general") -> Result:
+                check_incremental=False, use_scene=True, initial_alignment="perturbed", local_solver="general",
+                weak_group="raise", tk_options=None) -> Result:
     """orthosfm::reconstruct from the views' descriptors on: one wall clock over matching,
     track building, group ordering and the incremental pose estimation.
     solver 0: quaternion cameras (ORTHO_QUATERNION); 1..3: Euler cameras with that many
     free angle blocks (3 = ORTHO_EULER_ALL_DOF: phi, theta, roll and the offsets).
-    verify: match_and_build_tracks' (True, False or "affine").  local_solver: run_pose_estimation's."""
+    verify: match_and_build_tracks' (True, False or "affine").  local_solver, weak_group, tk_options:
+    run_pose_estimation's."""
     tm = Timings()
     t_all = time.perf_counter()
     tt, info = match_and_build_tracks(iset, matcher, device, verify, tm)
     model = B.MODEL_QUATERNION if solver == 0 else B.MODEL_EULER
-    alignments = []
+    alignments, resected = [], []
     cams, aligned, groups, calls, captured = run_pose_estimation(
         tt, iset, model, device, rot_perturb_deg, off_perturb, seed, tm, capture, max_groups, verbose,
         euler_dof=euler_dof_of_solver(solver), check_incremental=check_incremental, use_scene=use_scene,
-        initial_alignment=initial_alignment, alignments=alignments, local_solver=local_solver)
+        initial_alignment=initial_alignment, alignments=alignments, local_solver=local_solver,
+        weak_group=weak_group, tk_options=tk_options, resected=resected)
     join_background()            # inside the clock: the matcher's memory is back when the job is done
     tm.total_s = time.perf_counter() - t_all
     info.pop("match_stats", None)
-    return Result(cams, aligned, tt, groups, tm, calls, captured=captured, initial_alignments=alignments, **info)
+    return Result(cams, aligned, tt, groups, tm, calls, captured=captured, initial_alignments=alignments, resected_groups=resected, **info)
 
 
 CAMERA_DISTANCE = 10.0                  # OrthoQuaternionCamera.cpp:70, OrthographicCamera.h:119

@@ -110,6 +110,20 @@ class Scene:
                                                 C.c_int32(inl.shape[0]), C.byref(r), C.byref(n)))
         return tk._alignment(b1, b2, off, inl, r, n.value)
 
+    def resect_view(self, view, stream_id=0, **opts):
+        """osfm_scene_resect_view: the affine-camera RANSAC (orthosfm_amd/resect.py) over the live features of `view`
+        whose track has a point, selected and gathered on the device.  The view needs no camera; the scene is not
+        changed."""
+        from . import resect
+        o = resect.options(**opts)
+        rot, off, scale = np.zeros((3, 3)), np.zeros(2), C.c_double()
+        inl = np.zeros(max(self.num_tracks, 1), dtype=np.uint8)        # a track holds at most one feature of a view
+        r, n = capi.ResectResult(), C.c_int32()
+        capi.check(capi.lib.osfm_scene_resect_view(self._h_scene, C.c_int32(view), C.byref(o), C.c_uint64(stream_id),
+                                                   rot.ctypes.data, C.byref(scale), off.ctypes.data, inl.ctypes.data,
+                                                   C.c_int32(inl.shape[0]), C.byref(r), C.byref(n)))
+        return resect._placement(rot, scale, off, inl, r, n.value)
+
     def global_adjustment(self, options):
         s = capi.BaSummary()
         m, o = C.c_int32(), C.c_int32()
