@@ -422,6 +422,59 @@ OSFM_API int osfm_ransac_affine(int device, const float *pos1, int n1, const flo
     const int32_t *corr, int k, const osfm_ransac_affine_options *opts, uint64_t pair_id,
     int32_t *inliers, int32_t *num_inliers, double *F, osfm_ransac_affine_result *result);
 
+/* Guided matching of verified pairs of ORTHOGRAPHIC views (no counterpart in the reference): the nearest-neighbour
+ * search of osfm_match_pair once more, restricted to the band |a x2 + b y2 + c x1 + d y1 + e| < threshold * sqrt(s)
+ * around the affine epipolar line of a pair whose F_A is known.  The ratio test against the whole other view throws
+ * repeated structure away (second ~ best); inside the band there is usually one candidate left.  Per pair:
+ *   F      row p of F when given ((a, b, c, d, e) = F[2], F[5], F[6], F[7], F[8]); else the least-squares F_A over all
+ *          seeds of the pair, which is osfm_ransac_affine's refit with every seed an inlier.  F NULL and fewer than 5
+ *          seeds: OSFM_GUIDED_TOO_FEW.  s = a^2 + b^2 + c^2 + d^2 not > 0 or a coefficient that is not finite:
+ *          OSFM_GUIDED_DEGENERATE.  Either way the pair's list is its seeds as given.  F_out receives the F used.
+ *   band   j of view_2 is a candidate of i of view_1, and i of j, when the match (i, j) passes osfm_ransac_affine's
+ *          own inlier test for F at `threshold`.  A feature that occurs in a seed is neither a query nor a candidate.
+ *   search per descriptor type (indices and offsets as osfm_match_pair), NearestNeighbor<T>::find over the candidate
+ *          rows in ascending feature index -- 16-bit lane sums, >= comparisons, T-typed state from (0, 0), the
+ *          reference's conversion to distances -- then the ratio test of matching.h:114-146 with the squared ratio
+ *          (0 / 0 accepted).  A query without candidates has no match.
+ *   cap    cap_from_seeds: per type, the largest converted distance of a seed's own descriptor product; a result with
+ *          dist_1st above it is dropped, and a type without seeds adds nothing.  (A lone distractor in the band passes
+ *          a ratio test that has no second candidate; the seeds say how far a true match can be.)
+ *   list   (i, j) is added when i -> j and j -> i.  The list holds the seeds and the additions, ascending in
+ *          feature_1; every feature occurs once at most.
+ * OSFM_E_ARG (nothing written): a view without positions, a seed out of range, a feature twice in a pair's seeds, a
+ * seed that joins a SIFT row to a SURF row, offsets that decrease, a threshold that is not > 0.  OSFM_E_CAPACITY with
+ * *total set as osfm_match_all.  A pair's results do not depend on what else is in the call, and a call repeats to
+ * the byte.  Only the bank and the positions are read, whatever the matcher type; a multi-device handle runs the
+ * call on its first shard. */
+typedef struct osfm_guided_options {
+    double  threshold;         /* 0.0015: the band, in the unit and by the test of osfm_ransac_affine's threshold */
+    float   sift_lowe_ratio;   /* 0.8f */
+    float   surf_lowe_ratio;   /* 0.7f */
+    int32_t cap_from_seeds;    /* 1 */
+    int32_t reserved;
+} osfm_guided_options;
+OSFM_API int osfm_guided_options_default(osfm_guided_options *o);
+
+enum { OSFM_GUIDED_OK = 0, OSFM_GUIDED_TOO_FEW = 1, OSFM_GUIDED_DEGENERATE = 2 };
+typedef struct osfm_guided_result {
+    int32_t status;            /* OSFM_GUIDED_* */
+    int32_t num_seeds;
+    int32_t num_added;         /* correspondences in the list that are not seeds */
+    int32_t max_candidates;    /* largest candidate count of one query of this pair (both directions, both types) */
+    int64_t offset;            /* first correspondence of the pair in corr */
+} osfm_guided_result;
+
+/* The kernel's own sizes: queries a workgroup carries, positions it stages at a time, candidates a query collects
+ * before they are scored (what the tests place their cases around). */
+OSFM_API int osfm_guided_limits(int32_t *queries_per_workgroup, int32_t *positions_per_chunk, int32_t *candidates_per_pass);
+
+/* seed_offsets [num_pairs + 1] in correspondences; seed_corr (feature_1, feature_2) pairs; F NULL or [num_pairs][9] in
+ * osfm_ransac_affine's layout; opts NULL: the defaults; F_out NULL or [num_pairs][9]. */
+OSFM_API int osfm_match_guided(osfm_matcher *m, const osfm_pair *pairs, int num_pairs,
+    const int64_t *seed_offsets, const int32_t *seed_corr, const double *F,
+    const osfm_guided_options *opts, osfm_guided_result *results,
+    int32_t *corr, int64_t capacity, int64_t *total, double *F_out);
+
 /* ====================================================================== */
 /* (B) Bundle adjustment                                                   */
 /* ====================================================================== */

@@ -69,6 +69,21 @@ class RansacAffineResult(C.Structure):
                 ("refit_ran", C.c_int32), ("refit_accepted", C.c_int32)]
 
 
+class GuidedOptions(C.Structure):
+    """osfm_guided_options"""
+    _fields_ = [("threshold", C.c_double), ("sift_lowe_ratio", C.c_float), ("surf_lowe_ratio", C.c_float),
+                ("cap_from_seeds", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GuidedResult(C.Structure):
+    """osfm_guided_result"""
+    _fields_ = [("status", C.c_int32), ("num_seeds", C.c_int32), ("num_added", C.c_int32),
+                ("max_candidates", C.c_int32), ("offset", C.c_int64)]
+
+
+GUIDED_OK, GUIDED_TOO_FEW, GUIDED_DEGENERATE = 0, 1, 2
+
+
 class Pair(C.Structure):
     _fields_ = [("view_1", C.c_int32), ("view_2", C.c_int32)]
 
@@ -274,6 +289,7 @@ EXPORTS = [
     "osfm_quantize_sift", "osfm_quantize_surf",
     "osfm_match_set_view", "osfm_match_set_view_float", "osfm_match_view_size", "osfm_match_expect_pairs", "osfm_match_set_positions",
     "osfm_ransac_options_default", "osfm_ransac_fundamental", "osfm_ransac_affine_options_default", "osfm_ransac_affine",
+    "osfm_guided_options_default", "osfm_guided_limits", "osfm_match_guided",
     "osfm_match_pair", "osfm_match_pair_lowres", "osfm_match_twoway", "osfm_match_all",
     "osfm_pair_from_index", "osfm_match_get_stats", "osfm_match_get_shard_stats", "osfm_match_get_cascade_hashes",
     "osfm_ba_options_default", "osfm_ba_small_limits", "osfm_ba_solve", "osfm_ba_reprojection_errors",
@@ -359,6 +375,9 @@ lib.osfm_resect_view.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.osfm_scene_resect_view.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+lib.osfm_guided_limits.argtypes = [C.POINTER(C.c_int32)] * 3
+lib.osfm_match_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GuidedOptions),
+                                  C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]
 lib.osfm_ba_debug_cholesky_solve.restype = C.c_int
 lib.osfm_ba_debug_cholesky_solve.argtypes = [C.c_int, C.c_int, _f64p, _f64p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, _f64p, _i32p, _i32p]
@@ -441,6 +460,19 @@ def default_match_options() -> MatchOptions:
     o = MatchOptions()
     check(lib.osfm_match_options_default_v2(C.byref(o)))      # the symbol the header binds: MatchOptions in full
     return o
+
+
+def default_guided_options() -> GuidedOptions:
+    o = GuidedOptions()
+    check(lib.osfm_guided_options_default(C.byref(o)))
+    return o
+
+
+def guided_limits():
+    """(queries_per_workgroup, positions_per_chunk, candidates_per_pass) of the guided matching kernel."""
+    a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib.osfm_guided_limits(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
 
 
 def default_sift_options() -> SiftOptions:

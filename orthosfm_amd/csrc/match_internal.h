@@ -2,7 +2,7 @@
 //   match_plan.hip   what a batch is cut into (pure host arithmetic)      match_batch.hip  run_batch: one batch on the device
 //   match_views.hip  view upload, hand-off, copies, cascade-hash build    match_all.hip    osfm_match_all on one device
 //   match_multi.hip  the multi-device front                               match_pair.hip   request combiner of the per-pair entries
-//   match_api.hip    set_error and every extern "C" entry
+//   match_api.hip    set_error and every extern "C" entry               guided_api.hip   osfm_match_guided
 #pragma once
 #include <atomic>
 #include <condition_variable>
@@ -45,6 +45,8 @@ struct osfm_matcher {
     hipEvent_t ev_compact[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
     bool copied_used[2] = {false, false};
     osfm::DeviceBuffer d_jobs, d_inl, d_inl_count, d_corr2, d_gather_off;
+    // osfm_match_guided (guided_api.hip): job and result records, seeds, band scalars, one-way results, padded and packed lists
+    osfm::DeviceBuffer g_jobs, g_prep, g_seeds, g_u, g_m, g_list, g_out, g_off;
     hipEvent_t ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     hipEvent_t ev_sp[2] = {nullptr, nullptr};
     // page-locked staging of the view uploads (two blocks alternate; the event says a block's transfer is done)

@@ -25,6 +25,9 @@ class MatchResult:
 _PAIR_RESULT_DTYPE = np.dtype([("status", np.int32), ("lowres_matches", np.int32), ("num_matches", np.int32),
                                ("num_inliers", np.int32), ("offset", np.int64)])
 assert _PAIR_RESULT_DTYPE.itemsize == C.sizeof(capi.PairResult)
+_GUIDED_RESULT_DTYPE = np.dtype([("status", np.int32), ("num_seeds", np.int32), ("num_added", np.int32),
+                                 ("max_candidates", np.int32), ("offset", np.int64)])
+assert _GUIDED_RESULT_DTYPE.itemsize == C.sizeof(capi.GuidedResult)
 
 
 @dataclass
@@ -219,6 +222,64 @@ class HipExhaustiveMatching:
         ra = np.frombuffer(res, dtype=_PAIR_RESULT_DTYPE, count=n)      # keeps `res` alive; one per call
         self._last_pairs_flat = flat
         return ra, corr
+
+    # --- guided matching inside the affine epipolar band (no counterpart in the reference) ---
+    def guided_match(self, pairs, seed_offsets, seed_corr, F=None, capacity=None, **options):
+        """osfm_match_guided as it is.  pairs (n, 2); seed_offsets (n + 1,) in correspondences; seed_corr (rows, 2);
+        F None (fitted to each pair's seeds) or (n, 3, 3) in ransac_affine's layout; options: the fields of
+        osfm_guided_options.  Returns (records, corr, F_used): one osfm_guided_result per pair as a numpy record, the
+        (total, 2) lists (pair k at corr[offset : offset + num_seeds + num_added]) and the (n, 3, 3) F of every pair."""
+        flat = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        n = flat.shape[0]
+        off = np.ascontiguousarray(seed_offsets, dtype=np.int64).reshape(-1)
+        assert off.shape[0] == n + 1, "guided_match: seed_offsets holds one entry more than there are pairs"
+        seeds = np.ascontiguousarray(seed_corr, dtype=np.int32).reshape(-1, 2)
+        o = capi.default_guided_options()
+        for k, v in options.items():
+            if k not in ("threshold", "sift_lowe_ratio", "surf_lowe_ratio", "cap_from_seeds"):
+                raise TypeError(f"guided_match: unknown option {k}")
+            setattr(o, k, int(v) if k == "cap_from_seeds" else v)
+        Fin = None if F is None else np.ascontiguousarray(F, dtype=np.float64).reshape(n, 9)
+        if capacity is None:
+            capacity = sum(min(sum(self.view_size(a)), sum(self.view_size(b))) for a, b in flat.tolist())
+        res = np.zeros(max(n, 1), dtype=_GUIDED_RESULT_DTYPE)
+        corr = np.zeros((max(capacity, 1), 2), dtype=np.int32)
+        Fout = np.zeros((max(n, 1), 9))
+        total = C.c_int64()
+        self.last_guided_total = None
+        status = capi.lib.osfm_match_guided(self._h, flat.ctypes.data, n, off.ctypes.data, seeds.ctypes.data if seeds.size else None,
+                                            Fin.ctypes.data if Fin is not None and Fin.size else None, C.byref(o), res.ctypes.data,
+                                            corr.ctypes.data, C.c_int64(capacity), C.byref(total), Fout.ctypes.data)
+        if status == capi.E_CAPACITY:
+            self.last_guided_total = int(total.value)
+        capi.check(status)
+        return res[:n], corr[:int(total.value)], Fout[:n].reshape(n, 3, 3)
+
+    def guided_arrays(self, pairs, records, corr, F=None, **options):
+        """Guided matching of what compute_arrays returned: every OSFM_PAIR_MATCHED pair goes through osfm_match_guided
+        with its list as seeds (F: None, or (n, 3, 3) with a row per pair of `pairs`).  Returns (records, corr, F_used):
+        a copy of `records` whose counts (num_inliers with verification, else num_matches) and offsets describe the
+        extended lists in the new corr, and the (n, 3, 3) F of every pair (zero where a pair was not guided).  The
+        osfm_guided_result records of the guided pairs and their positions in `pairs` are left in self.last_guided."""
+        flat = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        assert flat.shape[0] == len(records), "guided_arrays: records and pair list of different calls"
+        cnt_field = "num_inliers" if self.opts.geometric_verification else "num_matches"
+        sel = np.nonzero(records["status"] == capi.PAIR_MATCHED)[0]
+        counts = records[cnt_field][sel].astype(np.int64)
+        offs = np.zeros(sel.size + 1, np.int64)
+        np.cumsum(counts, out=offs[1:])
+        corr = np.asarray(corr).reshape(-1, 2)
+        seeds = np.concatenate([corr[o:o + c] for o, c in zip(records["offset"][sel].tolist(), counts.tolist())] +
+                               [np.zeros((0, 2), np.int32)]).astype(np.int32)
+        Fsel = None if F is None else np.asarray(F, dtype=np.float64).reshape(-1, 3, 3)[sel]
+        gres, gcorr, Fg = self.guided_match(flat[sel], offs, seeds, Fsel, **options)
+        out = records.copy()
+        out[cnt_field][sel] = gres["num_seeds"] + gres["num_added"]
+        out["offset"][sel] = gres["offset"]
+        Fused = np.zeros((flat.shape[0], 3, 3))
+        Fused[sel] = Fg
+        self.last_guided = (sel, gres)
+        return out, gcorr, Fused
 
     def compute(self, pairs=None, capacity=None):
         """Matches `pairs` (default: all V(V-1)/2 pairs in the reference's

@@ -338,6 +338,7 @@ class Timings:
     upload_s: float = 0.0
     setup_s: float = 0.0          # inside matching_s: creating the matcher, waiting for the page-locked list buffers
     matching_s: float = 0.0
+    guided_s: float = 0.0         # inside matching_s: osfm_match_guided on the verified pairs (guided=True)
     tracks_s: float = 0.0
     tracks_busy_s: float = 0.0
     convert_s: float = 0.0
@@ -427,9 +428,12 @@ class _ListBufferPool:
 _list_buffers = _ListBufferPool()
 
 
-def match_and_build_tracks(iset, matcher="exhaustive", device=0, verify=True, timings=None, pairs=None):
+def match_and_build_tracks(iset, matcher="exhaustive", device=0, verify=True, timings=None, pairs=None, guided=False,
+                           options=None):
     """calculateTracksUsingMVE up to (and including) the track conversion.  verify: True -- RANSAC-F as the reference;
-    "affine" -- the affine RANSAC for orthographic views; False -- none.  info["verification"] names the model used."""
+    "affine" -- the affine RANSAC for orthographic views; False -- none.  info["verification"] names the model used.
+    guided: every verified pair goes through osfm_match_guided before the tracks are built (_match_and_build).
+    options: the capi.MatchOptions to start from, as tracks_from_images'."""
     W, H = iset.width, iset.height
 
     def upload(m, v):
@@ -442,20 +446,21 @@ def match_and_build_tracks(iset, matcher="exhaustive", device=0, verify=True, ti
         return xy
 
     sizes = np.array([iset.sift[v].shape[0] + iset.surf[v].shape[0] for v in range(iset.num_views)], dtype=np.int32)
-    tt, info, _ = _match_and_build(iset.num_views, upload, sizes, lambda: W, matcher, device, verify, timings, pairs, None, None)
+    tt, info, _ = _match_and_build(iset.num_views, upload, sizes, lambda: W, matcher, device, verify, timings, pairs, options, None,
+                                   guided=guided)
     return tt, info
 
 
 def tracks_from_images(images, matcher="exhaustive", device=0, verify=True, downscale_factor=1, max_image_size=6_000_000,
                        options=None, timings=None, pairs=None, masks=None, mask_mode="tracks", mask_clamp="reference",
-                       feature_colors=False):
+                       feature_colors=False, guided=False):
     """calculateTracksUsingMVE from decoded images onwards: every image (uint8 [h, w] or [h, w, 3]) goes through a
     features.ViewFrontEnd -- the halving chain, SIFT and SURF, colours and normalised positions on the device -- and
     from there into the matcher without the descriptors' way through the host; then matching, RANSAC-F, the tracks
     and the reference's pixel conversion, import_width * (pos + 0.5) on BOTH axes with pos normalised by the size of
     the feature image (matching_mve.cpp:455-466; import_width is the last view's, as the reference's imageWidth is
     whichever view wrote it last).  verify: as match_and_build_tracks.  options: the capi.MatchOptions to start from (geometric_verification and the
-    matcher type are set here).  Returns (TrackTable, track colours (num_tracks, 3) uint8, info).
+    matcher type are set here); guided: as match_and_build_tracks.  Returns (TrackTable, track colours (num_tracks, 3) uint8, info).
 
     masks: one uint8 mask [mh, mw] or None per image, the reference's --mask-folder (reconstruct.cpp:47-53).  With
     mask_mode "tracks" the tracks go through filterTracksWithMasks: a track with a feature where its view's mask is
@@ -503,7 +508,7 @@ def tracks_from_images(images, matcher="exhaustive", device=0, verify=True, down
 
     try:
         tt, info, tcol = _match_and_build(V, upload, None, lambda: width[0], matcher, device, verify, timings, pairs,
-                                          options, colors)
+                                          options, colors, guided=guided)
     finally:
         front.close()
     if not marked:
@@ -527,12 +532,18 @@ def tracks_from_images(images, matcher="exhaustive", device=0, verify=True, down
     return tt, tcol, info
 
 
-def _match_and_build(V, upload, sizes, image_width, matcher, device, verify, timings, pairs, options, colors):
+def _match_and_build(V, upload, sizes, image_width, matcher, device, verify, timings, pairs, options, colors, guided=False):
     """The body of match_and_build_tracks with the upload of a view as a parameter: upload(m, v) sets view v of the
     matcher (its positions too) and returns the view's normalised positions.  sizes: the features per view, or None
     where only the uploads know them (the matching then starts when every view is there).  image_width() is asked
-    after the uploads; colors: None, or a list the uploads fill with FeatureSet::colors per view."""
+    after the uploads; colors: None, or a list the uploads fill with FeatureSet::colors per view.
+
+    guided: the OSFM_PAIR_MATCHED pairs of every batch go through osfm_match_guided with their verified lists as seeds
+    (F_A fitted to the seeds), and the tracks are built from the extended lists; needs a verification, else ValueError.
+    info["guided"] has the counts.  This step has no counterpart in the reference."""
     tm = timings if timings is not None else Timings()
+    if guided and not verify:
+        raise ValueError("guided=True extends VERIFIED lists: verify must be True or \"affine\"")
     if options is not None:
         o = capi.MatchOptions.from_buffer_copy(options)
     else:
@@ -631,10 +642,10 @@ def _match_and_build(V, upload, sizes, image_width, matcher, device, verify, tim
             item = work.get()
             if item is None:
                 return
-            sub, ra, corr_buf = item
+            sub, ra, lists, corr_buf = item
             t1 = time.perf_counter()
             try:
-                builder.feed(sub, ra, corr_buf)
+                builder.feed(sub, ra, lists)
             except Exception as e:      # reported by the main thread
                 err.append(e)
             tracks_busy[0] += time.perf_counter() - t1
@@ -643,6 +654,7 @@ def _match_and_build(V, upload, sizes, image_width, matcher, device, verify, tim
     th = threading.Thread(target=merge_worker, daemon=True)
     th.start()
     status = np.zeros(pf.shape[0], dtype=np.int32)
+    ginfo = {"pairs": 0, "seeds": 0, "added": 0, "status": {"ok": 0, "too_few": 0, "degenerate": 0}}
     for k in range(n_batches):
         sub = pf[bounds[k]:bounds[k + 1]]
         t1 = time.perf_counter()
@@ -660,7 +672,19 @@ def _match_and_build(V, upload, sizes, image_width, matcher, device, verify, tim
         m.use_result_buffer(buf)
         ra, corr_buf = m.compute_arrays(sub, capacity=max_cap)
         status[bounds[k]:bounds[k + 1]] = ra["status"]
-        work.put((sub, ra.copy(), buf))
+        if guided:
+            t1 = time.perf_counter()
+            ra, lists, _ = m.guided_arrays(sub, ra, corr_buf)
+            gsel, gres = m.last_guided
+            ginfo["pairs"] += int(gsel.size)
+            ginfo["seeds"] += int(gres["num_seeds"].sum())
+            ginfo["added"] += int(gres["num_added"].sum())
+            for name, code in (("ok", capi.GUIDED_OK), ("too_few", capi.GUIDED_TOO_FEW), ("degenerate", capi.GUIDED_DEGENERATE)):
+                ginfo["status"][name] += int((gres["status"] == code).sum())
+            tm.guided_s += time.perf_counter() - t1
+            work.put((sub, ra, lists, buf))
+        else:
+            work.put((sub, ra.copy(), buf, buf))
     wait_for_views(V)
     up_thread.join()
     # upload_s: what the job waited for views (before the first batch and between batches); the rest of
@@ -691,6 +715,8 @@ def _match_and_build(V, upload, sizes, image_width, matcher, device, verify, tim
             "pair_status": status,
             "verification": "none" if not o.geometric_verification else
                             "affine" if o.ransac_model == capi.RANSAC_AFFINE else "fundamental"}
+    if guided:
+        info["guided"] = ginfo
     try:
         st = m.stats()
         info["match_stats"] = {f[0]: getattr(st, f[0]) for f in st._fields_ if not f[0].startswith("reserved")}
@@ -1138,16 +1164,16 @@ def _global_ba(tt, model, cams, const, aligned, W, H, V, solve, kind, opt, tm):
 def reconstruct(iset, solver=0, matcher="exhaustive", device=0, verify=True, rot_perturb_deg=2.0,
                 off_perturb=0.01, seed=7, capture=(), max_groups=None, verbose=False,
                 check_incremental=False, use_scene=True, initial_alignment="perturbed", local_solver="general",
-                weak_group="raise", tk_options=None) -> Result:
+                weak_group="raise", tk_options=None, guided=False) -> Result:
     """orthosfm::reconstruct from the views' descriptors on: one wall clock over matching,
     track building, group ordering and the incremental pose estimation.
     solver 0: quaternion cameras (ORTHO_QUATERNION); 1..3: Euler cameras with that many
     free angle blocks (3 = ORTHO_EULER_ALL_DOF: phi, theta, roll and the offsets).
-    verify: match_and_build_tracks' (True, False or "affine").  local_solver, weak_group, tk_options:
+    verify, guided: match_and_build_tracks' (True, False or "affine"; guided matching of the verified pairs).  local_solver, weak_group, tk_options:
     run_pose_estimation's."""
     tm = Timings()
     t_all = time.perf_counter()
-    tt, info = match_and_build_tracks(iset, matcher, device, verify, tm)
+    tt, info = match_and_build_tracks(iset, matcher, device, verify, tm, guided=guided)
     model = B.MODEL_QUATERNION if solver == 0 else B.MODEL_EULER
     alignments, resected = [], []
     cams, aligned, groups, calls, captured = run_pose_estimation(
