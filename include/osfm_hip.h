@@ -651,6 +651,76 @@ typedef struct osfm_ba_lin_capture {
  * solve's launches and their order are the same.  osfm_ba_solve itself copies nothing. */
 OSFM_API int osfm_ba_debug_linearization(const osfm_ba_problem *p, const osfm_ba_options *o, osfm_ba_lin_capture *cap);
 
+/* ---- covariances of the adjusted cameras and points (the counterpart of ceres::Covariance on the reference's problem,
+ * which the reference never calls) ----
+ *
+ * One linearisation at the problem's cameras and points AS GIVEN (no step is taken, nothing is modified).  J is the
+ * Jacobian of the Huber-corrected residuals (the rows the solve linearises: apply_loss_function = true) in the solve's
+ * tangent space -- camera columns: the free tangent columns in the cameras' own order (rotation, then offX / offY /
+ * scale; osfm_ba_lin_capture's layout), point columns: the three tangent columns of the homogeneous point.  The
+ * cofactor matrix Q = (J^T J)^-1 is computed through the Schur complement S = U - sum_j W_j V_j^-1 W_j^T with NO
+ * Levenberg-Marquardt diagonal.  The matrices are returned unscaled: multiplying by variance_factor is the caller's.
+ *
+ * Gauge.  With one camera constant and the scales constant (what the reference's reconstruction produces) J^T J
+ * still has one null direction: a translation of the scene along that camera's viewing axis, which every other camera
+ * absorbs in its offsets.  depth_gauge != 0: if some camera has every block constant, ONE further offset is treated
+ * as constant for this call -- with c0 the first all-constant camera, of the cameras with both offsets free the one
+ * whose viewing axis makes the largest angle with c0's (as lines: the smallest |cosine|; ties: the lowest index),
+ * and of its two image axes the one with the larger component along c0's viewing axis (ties: X).  The choice is
+ * reported as gauge_camera / gauge_axis (0: offX, 1: offY; -1 / -1: nothing held).  THE HELD COLUMN COUNTS AS
+ * CONSTANT in cam_ldim, nc and every output.  depth_gauge == 0: the masks are used exactly as given.
+ *
+ * Rank.  After the factorisation of S the smallest relative pivot min_i L_ii^2 / S_ii (S_ii: S's own diagonal
+ * before elimination) is compared with min_pivot_ratio: below it the call returns OSFM_E_NUMERIC with
+ * rank_deficient = 1 and min_pivot_seen set, and writes no covariance.  The same ratio is applied to the pivots of
+ * the 3 x 3 V_j of every point.
+ *
+ * A point is invalid (point_valid 0, covariance zero) when it has fewer than two observations, when |w| < 1e-12 |x|
+ * (|x|: the 2-norm of the homogeneous 4-vector), or when V_j fails the pivot test (parallel rays).  An invalid point
+ * is LEFT OUT of the system: every other output is what the problem without that track gives.
+ * With optimize_points == 0, S = U, nothing is left out and the point outputs are not written.
+ * At most OSFM_BA_COV_MAX_UNKNOWNS camera unknowns (the inverse works on three dense N x N arrays): beyond that
+ * OSFM_E_CAPACITY. */
+#define OSFM_BA_COV_MAX_UNKNOWNS 8192
+typedef struct osfm_ba_cov_options {
+    double huber_delta;           /* 1.0 */
+    double min_pivot_ratio;       /* 1e-8 */
+    int32_t optimize_points;      /* 1 */
+    int32_t depth_gauge;          /* 1 */
+    int32_t device;               /* 0 */
+    int32_t reserved;
+} osfm_ba_cov_options;
+
+typedef struct osfm_ba_cov_result {
+    /* set by the caller; any pointer may be NULL (that output is not written) */
+    double *cam_cov;              /* [C][6][6] the camera's diagonal block of S^-1 in its first cam_ldim rows / columns, zero elsewhere */
+    int32_t *cam_ldim;            /* [C] free tangent columns per camera (the held gauge column is not among them) */
+    double *cam_cov_full;         /* [nc][nc] the whole S^-1, symmetric, cameras in the caller's order */
+    double *point_cov;            /* [M][3][3] covariance of the Euclidean point (x/w, y/w, z/w): G (V_j^-1 + Y_j^T S^-1 Y_j) G^T */
+    uint8_t *point_valid;         /* [M] */
+    int32_t nc;                   /* the nc cam_cov_full is sized for (read when cam_cov_full != NULL: OSFM_E_ARG when
+                                   * the problem's layout, gauge column held, has another; num_camera_unknowns and
+                                   * the gauge fields then say what the layout has, nothing else is written) */
+    int32_t reserved;
+    /* filled in by the call */
+    double cost;                  /* 1/2 sum rho over the observations of the system */
+    double variance_factor;       /* 2 cost / (num_residuals - num_unknowns), 0 when that is not positive */
+    double min_pivot_seen;        /* smallest relative pivot of S */
+    int32_t num_residuals, num_unknowns;
+    int32_t num_camera_unknowns;  /* nc */
+    int32_t num_valid_points;
+    int32_t gauge_camera, gauge_axis;
+    int32_t rank_deficient;
+    int32_t dense_schur;          /* the point part of S came from the dense product (dense visibility) */
+    /* device time per kernel family (HIP events) and the wall time of the whole call */
+    double linearize_ms, factor_ms, inverse_ms, point_ms, total_ms;
+} osfm_ba_cov_result;
+
+OSFM_API int osfm_ba_cov_options_default(osfm_ba_cov_options *opts);
+/* The problem is validated as for osfm_ba_solve (a repeated (camera, point) is refused) and is not modified.
+ * opts NULL: the defaults.  On OSFM_E_NUMERIC (rank deficient) the scalar fields are filled in, the arrays untouched. */
+OSFM_API int osfm_ba_covariance(const osfm_ba_problem *p, const osfm_ba_cov_options *opts, osfm_ba_cov_result *res);
+
 /* Batched ReconstructionAlgorithm::evaluateReprojectionError
  * (OrthoQuaternionRecoAlgorithm.cpp:175-194,
  * OrthographicReconstructionAlgorithm.cpp:204-223): err[k] = ||r_k||_2 in
@@ -740,6 +810,11 @@ OSFM_API int osfm_scene_local_adjustment(osfm_scene *s, int n, const int32_t *vi
  * track with a point, every live feature of it whose view has a camera; cameras and points updated in the scene. */
 OSFM_API int osfm_scene_global_adjustment(osfm_scene *s, const osfm_ba_options *opt, osfm_ba_summary *sum, int32_t *num_points,
     int32_t *num_observations);
+/* osfm_ba_covariance on exactly the selection osfm_scene_global_adjustment makes (alive tracks with a point, live
+ * features of aligned views), bit for bit what the per-call entry gives on that problem.  Cameras in join order (C =
+ * the aligned cameras); point_cov / point_valid per scene track in the caller's numbering ([num_tracks] as given to
+ * osfm_scene_create; a track outside the selection is invalid, zero).  The scene is not changed. */
+OSFM_API int osfm_scene_covariance(osfm_scene *s, const osfm_ba_cov_options *opts, osfm_ba_cov_result *res);
 /* filterOutlierTracks over the alive tracks (outlier_filtering.cpp:40-125); what it drops loses its flag */
 OSFM_API int osfm_scene_filter_outliers(osfm_scene *s, osfm_outlier_stats *stats, int32_t *num_killed);
 /* the scene's state back: alive flags per track / feature, hasPoint() and point [num_tracks][4] (any may be NULL) */

@@ -170,6 +170,108 @@ def solve(problem: FlatProblem, options: capi.BaOptions | None = None, **kw) -> 
     return s
 
 
+@dataclass
+class Covariance:
+    """What osfm_ba_covariance / osfm_scene_covariance return (include/osfm_hip.h): the cofactor matrices, unscaled --
+    multiply by variance_factor for covariances in pixel units of the residuals.  An array that was not asked for
+    (skip=...) or not computed (cam_cov_full without full=True, the point arrays with optimize_points=0) is None."""
+    cam_cov: np.ndarray | None            # (C, 6, 6)
+    cam_ldim: np.ndarray | None           # (C,)
+    cam_cov_full: np.ndarray | None       # (nc, nc)
+    point_cov: np.ndarray | None          # (M, 3, 3) of the Euclidean point
+    point_valid: np.ndarray | None        # (M,) bool
+    cost: float
+    variance_factor: float
+    num_residuals: int
+    num_unknowns: int
+    num_camera_unknowns: int
+    num_valid_points: int
+    gauge_camera: int
+    gauge_axis: int
+    min_pivot_seen: float
+    rank_deficient: int
+    dense_schur: int
+    timings_ms: dict
+
+    def point_sigma(self) -> np.ndarray:
+        """sqrt(variance_factor * largest eigenvalue of point_cov) per point, NaN where the point is invalid."""
+        out = np.full(self.point_cov.shape[0], np.nan)
+        ok = self.point_valid
+        if ok.any():
+            out[ok] = np.sqrt(self.variance_factor * np.linalg.eigvalsh(self.point_cov[ok])[:, -1].clip(min=0.0))
+        return out
+
+
+def cov_options(**kw) -> capi.BaCovOptions:
+    """osfm_ba_cov_options_default with fields replaced (huber_delta, min_pivot_ratio, optimize_points, depth_gauge,
+    device)."""
+    o = capi.BaCovOptions()
+    capi.check(capi.lib.osfm_ba_cov_options_default(C.byref(o)))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def _covariance_call(call, num_cameras, num_points, nc_guess, o, full, skip, fill=None):
+    """Runs call(options, result) with arrays for num_cameras cameras / num_points points (skip: names of
+    capi.BaCovResult.ARRAYS passed as NULL; fill: a value the arrays start with).  cam_cov_full is sized for nc_guess
+    and, if the library's layout has another nc, for the one it reports."""
+    Cn, M = int(num_cameras), int(num_points)
+    with_points = bool(o.optimize_points)
+    nc = int(nc_guess)
+    for _ in range(2):
+        arrays = {"cam_cov": np.zeros((Cn, 6, 6)), "cam_ldim": np.zeros(Cn, dtype=np.int32),
+                  "cam_cov_full": np.zeros((nc, nc)) if full else None,
+                  "point_cov": np.zeros((M, 3, 3)) if with_points else None,
+                  "point_valid": np.zeros(M, dtype=np.uint8) if with_points else None}
+        for k in skip:
+            arrays[k] = None
+        r = capi.BaCovResult()
+        for k, a in arrays.items():
+            if a is not None and fill is not None:
+                a[...] = fill
+            # (an empty array still gets a pointer: NULL means "not asked for")
+            setattr(r, k, None if a is None else (a.ctypes.data if a.size else np.zeros(1).ctypes.data))
+        r.nc = nc
+        status = call(o, r)
+        if status == capi.E_ARG and arrays["cam_cov_full"] is not None and r.num_camera_unknowns != nc:
+            nc = int(r.num_camera_unknowns)
+            continue
+        break
+    if status != capi.OK:
+        err = capi.OsfmError(status, capi.last_error())
+        err.rank_deficient = int(r.rank_deficient) if status == capi.E_NUMERIC else 0
+        err.min_pivot_seen = float(r.min_pivot_seen)
+        err.gauge_camera, err.gauge_axis = int(r.gauge_camera), int(r.gauge_axis)
+        err.arrays = arrays
+        raise err
+    if arrays["point_valid"] is not None:
+        arrays["point_valid"] = arrays["point_valid"].astype(bool)
+    return Covariance(arrays["cam_cov"], arrays["cam_ldim"], arrays["cam_cov_full"], arrays["point_cov"], arrays["point_valid"],
+                      r.cost, r.variance_factor, r.num_residuals, r.num_unknowns, r.num_camera_unknowns, r.num_valid_points,
+                      r.gauge_camera, r.gauge_axis, r.min_pivot_seen, r.rank_deficient, r.dense_schur,
+                      {"linearize": r.linearize_ms, "factor": r.factor_ms, "inverse": r.inverse_ms, "point": r.point_ms,
+                       "total": r.total_ms})
+
+
+def covariance(problem: FlatProblem, options: capi.BaCovOptions | None = None, full: bool = False, skip=(), fill=None,
+               **kw) -> Covariance:
+    """osfm_ba_covariance: the cofactor matrices of the cameras and points at the problem's values, which are not
+    modified (include/osfm_hip.h: the gauge, the rank test, which points are invalid).  full: also the whole S^-1.
+    Raises capi.OsfmError; on E_NUMERIC (an open gauge) the error carries rank_deficient = 1 and min_pivot_seen."""
+    o = options if options is not None else cov_options(**kw)
+    st = problem.struct()
+    free = _free_columns(problem)
+    held = bool(o.depth_gauge) and bool((free == 0).any()) and bool(_both_offsets_free(problem).any())
+    return _covariance_call(lambda oo, r: capi.lib.osfm_ba_covariance(C.byref(st), C.byref(oo), C.byref(r)),
+                            problem.cam_params.shape[0], problem.points.shape[0], int(free.sum()) - int(held), o, full, skip, fill)
+
+
+def _both_offsets_free(problem: FlatProblem) -> np.ndarray:
+    cc = problem.cam_const
+    return (cc[:, 4:6] == 0).all(axis=1) if problem.model == 0 else (cc[:, 3:5] == 0).all(axis=1)
+
+
 FORM_AS_SOLVE, FORM_PER_COLUMN = 0, 1
 _LAUNCH_FIELDS = ("one_launch", "groups", "num_d", "num_p", "num_tiles", "arcs", "span", "nblk")
 

@@ -281,6 +281,24 @@ class BaLinCapture(C.Structure):
                                          "one_launch", "post_fused", "back_fused")]
 
 
+class BaCovOptions(C.Structure):
+    """osfm_ba_cov_options."""
+    _fields_ = [("huber_delta", C.c_double), ("min_pivot_ratio", C.c_double), ("optimize_points", C.c_int32),
+                ("depth_gauge", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BaCovResult(C.Structure):
+    """osfm_ba_cov_result: the caller's arrays (any may be None), then what the call fills in."""
+    ARRAYS = ("cam_cov", "cam_ldim", "cam_cov_full", "point_cov", "point_valid")
+    _fields_ = [(n, C.c_void_p) for n in ARRAYS] + [("nc", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, C.c_double) for n in ("cost", "variance_factor", "min_pivot_seen")] + \
+               [(n, C.c_int32) for n in ("num_residuals", "num_unknowns", "num_camera_unknowns", "num_valid_points",
+                                         "gauge_camera", "gauge_axis", "rank_deficient", "dense_schur")] + \
+               [(n, C.c_double) for n in ("linearize_ms", "factor_ms", "inverse_ms", "point_ms", "total_ms")]
+
+
+BA_COV_MAX_UNKNOWNS = 8192
+
 # every symbol include/osfm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "osfm_last_error", "osfm_version", "osfm_device_count", "osfm_device_memory", "osfm_library_memory", "osfm_trim_device_memory", "osfm_ransac_selfcheck", "osfm_ba_debug_chol_trace", "osfm_ba_debug_flow_spin_limit", "osfm_ba_debug_order",
@@ -293,7 +311,7 @@ EXPORTS = [
     "osfm_match_pair", "osfm_match_pair_lowres", "osfm_match_twoway", "osfm_match_all",
     "osfm_pair_from_index", "osfm_match_get_stats", "osfm_match_get_shard_stats", "osfm_match_get_cascade_hashes",
     "osfm_ba_options_default", "osfm_ba_small_limits", "osfm_ba_solve", "osfm_ba_reprojection_errors",
-    "osfm_ba_triangulate",
+    "osfm_ba_triangulate", "osfm_ba_cov_options_default", "osfm_ba_covariance", "osfm_scene_covariance",
     "osfm_nn_distances", "osfm_filter_outlier_tracks", "osfm_filter_reprojection",
     "osfm_scene_create", "osfm_scene_destroy", "osfm_scene_set_flags", "osfm_scene_align_views", "osfm_scene_set_cameras", "osfm_scene_get_cameras",
     "osfm_scene_triangulate", "osfm_scene_filter_reprojection", "osfm_scene_local_adjustment", "osfm_scene_global_adjustment",
@@ -378,6 +396,9 @@ lib.osfm_scene_resect_view.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_ui
 lib.osfm_guided_limits.argtypes = [C.POINTER(C.c_int32)] * 3
 lib.osfm_match_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GuidedOptions),
                                   C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]
+lib.osfm_ba_cov_options_default.argtypes = [C.POINTER(BaCovOptions)]
+lib.osfm_ba_covariance.argtypes = [C.c_void_p, C.POINTER(BaCovOptions), C.POINTER(BaCovResult)]
+lib.osfm_scene_covariance.argtypes = [C.c_void_p, C.POINTER(BaCovOptions), C.POINTER(BaCovResult)]
 lib.osfm_ba_debug_cholesky_solve.restype = C.c_int
 lib.osfm_ba_debug_cholesky_solve.argtypes = [C.c_int, C.c_int, _f64p, _f64p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, _f64p, _i32p, _i32p]

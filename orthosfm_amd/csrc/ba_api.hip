@@ -150,6 +150,13 @@ void build_camera_layout(int model, int C, const uint8_t *cam_const, Layout *L)
     L->nc = tot;
 }
 
+int validate_ba_problem(const osfm_ba_problem *p, const char *what, Layout *L) { return validate_problem(p, what, L); }
+
+int upload_ba_problem(const osfm_ba_problem *p, const Layout &L, double huber, int pdim, hipStream_t s, DeviceProblem *D)
+{
+    return upload_problem(p, L, huber, pdim, s, D);
+}
+
 int finish_device_problem(int model, int C, int M, int O, int nc, double huber, int pdim, hipStream_t s, DeviceProblem *D)
 {
     OSFM_RETURN_IF(D->cams[1].alloc((size_t)7 * C * 8));

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <functional>
 #include <utility>
 #include <vector>
 
@@ -74,6 +75,12 @@ void build_camera_layout(int model, int C, const uint8_t *cam_const, Layout *L);
 // candidate buffers and the per-observation point index
 int finish_device_problem(int model, int C, int M, int O, int nc, double huber, int pdim, hipStream_t s, DeviceProblem *D);
 
+// osfm_ba_solve's checks of a caller's problem (sizes, model, null arrays, observation ranges and order, one observation
+// per camera and point) with the caller's layout, and its upload into a finished DeviceProblem (L, which may have been
+// rebuilt from other constancy masks, has to outlive the stream's next synchronisation)
+int validate_ba_problem(const osfm_ba_problem *p, const char *what, Layout *L);
+int upload_ba_problem(const osfm_ba_problem *p, const Layout &L, double huber, int pdim, hipStream_t s, DeviceProblem *D);
+
 // The Levenberg-Marquardt solve (ba_solve.hip) on a finished DeviceProblem (start values in cams[0] / points[0]), which it
 // leaves as it was.  pair_bound: an upper bound of the Schur pair entries (sum of squared track lengths), refused beyond
 // 2^31 - 1.  On return *cur names the buffer pair (cams[cur], points[cur]) that holds the result; the stream is
@@ -130,6 +137,24 @@ inline std::vector<int32_t> unknown_positions(int C, const int32_t *ldim, const 
     }
     return pos;
 }
+
+// One linearisation of a finished DeviceProblem at its own cameras and points with the LM term OFF, by the solve's point
+// and pair passes: radius = infinity makes every diagonal's share diag / radius an exact zero, so the kernels run as they
+// are; unit Jacobi scales, the cameras' own order, launch-per-column Cholesky buffers.  What the passes left (all on
+// the device, alive while the callbacks run):
+struct PlainLin {
+    const double *obsrec;         // [O][kObsRec] Jc, Jp, Q = Jp V_j^-1, r per observation (unscaled)
+    const double *vinv;           // [9 M] V_j^-1
+    const int32_t *obs_lay;       // [O] cam_off | cam_ldim << 24 of the observation's camera
+    const double *cost_partials;  // [num_windows] the windows' shares of the cost, to be added in order
+    int num_windows;
+    CholeskyBuffers *chol;        // S (lower triangle blocks, identity on the padding diagonal) after the pair pass
+    bool dense;                   // S's point part came from the dense product
+};
+// after_points runs behind the point pass (nonzero: returned as it is, nothing else happens), after_system behind the
+// pair pass.  Neither stage synchronises.
+int ba_linearize_plain(const DeviceProblem &D, StreamLease &sg, int64_t pair_bound,
+    const std::function<int(const PlainLin &)> &after_points, const std::function<int(const PlainLin &)> &after_system);
 
 using Clock = std::chrono::steady_clock;
 inline void lap(int verbose, Clock::time_point t0, const char *what)       // verbose >= 2: the time since t0 on stderr

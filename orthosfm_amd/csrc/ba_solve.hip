@@ -472,6 +472,41 @@ int check_small_form(const osfm_ba_options &o, int num_cameras, bool capture, co
     return OSFM_OK;
 }
 
+int ba_linearize_plain(const DeviceProblem &D, StreamLease &sg, int64_t pair_bound,
+    const std::function<int(const PlainLin &)> &after_points, const std::function<int(const PlainLin &)> &after_system)
+{
+    Switches sw{};
+    sw.order = 0; sw.steps = true;       // the cameras' own order; no hand-off flags (the launch-per-column Cholesky)
+    hipStream_t s = sg.s;
+    BaDev d = D.dev;                     // (lm stays null: the kernels read the plain pointers and these arguments)
+    OSFM_RETURN_IF(sg.set->ensure_pinned(sizeof(LmDev)));
+    osfm_ba_summary sum;
+    memset(&sum, 0, sizeof(sum));
+    SystemLayout y;
+    OSFM_RETURN_IF(lay_out_system(d, sw, pair_bound, static_cast<int32_t *>(sg.set->pinned), s, y, &sum));
+    Workspace w;
+    OSFM_RETURN_IF(allocate_workspace(d, y, sw, s, w));
+    osfm_ba_options o;
+    osfm_ba_options_default(&o);
+    LmRun r = make_run(d, o, sw, y, w, sg.set->events, 0);
+    const double inf = std::numeric_limits<double>::infinity();
+    r.pa.mode = kPassNormal; r.pa.update_diag = 1; r.pa.want_gradient = 0; r.pa.radius = inf;
+    r.qa.mode = kPassNormal; r.qa.update_diag = 1; r.qa.want_gradient = 0; r.qa.radius = inf;
+    launch_point_pass(r.d, r.pa, y.win, s);
+    OSFM_HIP_CHECK(hipGetLastError());
+    const PlainLin lin{w.obsrec.as<double>(), w.vinv.as<double>(), y.win.obs_lay, w.partA.as<double>(), y.win.num, &w.chol, y.PL.dense};
+    const int rc = after_points(lin);
+    if (rc != 0) return rc;
+    launch_reset_system(w.chol.S.as<double>(), w.chol.s_elems, w.chol.N, y.span, w.chol.N, s);
+    if (y.PL.dense)
+        launch_schur_dense(r.d, w.obsrec.as<double>(), y.win.obs_lay, w.dense_z.as<double>(), w.dense_w.as<double>(),
+            w.dense_partial.as<double>(), w.chol.S.as<double>(), w.chol.N, true, s);
+    memset(&r.qa.post, 0, sizeof(r.qa.post));
+    launch_pair_pass(r.d, r.qa, s);
+    OSFM_HIP_CHECK(hipGetLastError());
+    return after_system(lin);
+}
+
 int ba_solve_core(const DeviceProblem &D, const osfm_ba_options &o, StreamLease &sg, int64_t pair_bound, osfm_ba_summary *sum,
     int *cur_out, osfm_ba_lin_capture *cap)
 {

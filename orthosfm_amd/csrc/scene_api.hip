@@ -29,6 +29,7 @@
 #include <mutex>
 #include <vector>
 
+#include "ba_cov.h"
 #include "ba_solve.h"
 #include "resect_kernels.h"
 #include "tk_kernels.h"
@@ -985,6 +986,84 @@ int osfm_scene_global_adjustment(osfm_scene *sc, const osfm_ba_options *opt, osf
     OSFM_HIP_CHECK(hipGetLastError());
     OSFM_HIP_CHECK(hipStreamSynchronize(s));
     sum->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return OSFM_OK;
+}
+
+int osfm_scene_covariance(osfm_scene *sc, const osfm_ba_cov_options *opts, osfm_ba_cov_result *res)
+{
+    if (!sc || !res) { set_error("scene_covariance: bad arguments"); return OSFM_E_ARG; }
+    osfm_ba_cov_result r = *res;
+    r.cost = r.variance_factor = r.min_pivot_seen = 0.0;
+    r.num_residuals = r.num_unknowns = r.num_camera_unknowns = r.num_valid_points = 0;
+    r.gauge_camera = r.gauge_axis = -1; r.rank_deficient = 0; r.dense_schur = 0;
+    r.linearize_ms = r.factor_ms = r.inverse_ms = r.point_ms = r.total_ms = 0.0;
+    osfm_ba_cov_options o;
+    if (opts) o = *opts; else osfm_ba_cov_options_default(&o);
+    std::lock_guard<std::mutex> lock(sc->mu);
+    OSFM_RETURN_IF(select_device(sc->device));
+    const int64_t F = sc->F;
+    const int T = sc->T, C = (int)sc->aligned.size();
+    // the gauge and the layout it leaves, from the host's mirror of the cameras
+    if (o.depth_gauge) cov_choose_gauge(sc->model, C, sc->h_cams.data(), sc->h_const.data(), &r.gauge_camera, &r.gauge_axis);
+    const std::vector<uint8_t> masks = cov_held_masks(sc->model, C, sc->h_const.data(), r.gauge_camera, r.gauge_axis);
+    Layout L;                 // (declared before the lease: the copies queued from it are waited for first)
+    build_camera_layout(sc->model, C, masks.data(), &L);
+    if (res->cam_cov_full && res->nc != L.nc) {
+        res->num_camera_unknowns = L.nc; res->gauge_camera = r.gauge_camera; res->gauge_axis = r.gauge_axis;     // (what it should have been)
+        set_error("scene_covariance: cam_cov_full is sized for %d camera columns, the scene's cameras have %d (the gauge column held)", res->nc, L.nc);
+        return OSFM_E_ARG;
+    }
+    Compact P;
+    StreamLease sg;
+    OSFM_RETURN_IF(sg.acquire());
+    hipStream_t s = sg.s;
+    // osfm_scene_global_adjustment's selection: every alive track with a point, every live feature of such a track whose
+    // view has a camera
+    int32_t *sel = sc->sel.as<int32_t>(), *scan = sc->scan.as<int32_t>(), *tflag = sc->tflag.as<int32_t>();
+    uint8_t *tmask = sc->aux_t2.as<uint8_t>();
+    hipLaunchKernelGGL(scene_track_flag_kernel, dim3(blocks_for(T + 1)), dim3(kThreads), 0, s, T, (int)kFlagAliveWithPoint, 0, nullptr,
+        sc->alive_t.as<uint8_t>(), sc->has_point.as<uint8_t>(), tflag);
+    hipLaunchKernelGGL(scene_to_byte_kernel, dim3(blocks_for(T)), dim3(kThreads), 0, s, T, tflag, tmask);
+    hipLaunchKernelGGL(scene_select_kernel, dim3(blocks_for(F + 1)), dim3(kThreads), 0, s, F, sc->feat_view.as<int32_t>(),
+        sc->track_of.as<int32_t>(), sc->alive_f.as<uint8_t>(), sc->alive_t.as<uint8_t>(), sc->cam_of_view.as<int32_t>(), tmask, sel);
+    OSFM_RETURN_IF(exclusive_scan(sc, sel, scan, F + 1, s));
+    int O = 0, M = 0;
+    OSFM_RETURN_IF(exclusive_scan(sc, tflag, sc->tslot.as<int32_t>(), (int64_t)T + 1, s));
+    OSFM_RETURN_IF(read_totals2(scan, F, sc->tslot.as<int32_t>(), T, s, &O, &M));
+    const int pdim = o.optimize_points ? 3 : 0;
+    OSFM_RETURN_IF(build_problem(sc, sel, scan, O, tflag, sc->point.as<double>(), C, nullptr, sc->cams.as<double>(), masks.data(),
+        sc->aligned.data(), sc->cam_of_view.as<int32_t>(), o.huber_delta, pdim, &L, s, &P, M));
+    const bool want_points = res->point_cov != nullptr || res->point_valid != nullptr;
+    CovHost h;
+    const int rc = ba_cov_core(P.D, o, sg, res->cam_cov != nullptr, res->cam_cov_full != nullptr, want_points, &r, &h);
+    if (rc == OSFM_OK || rc == OSFM_E_NUMERIC) {
+        const osfm_ba_cov_result keep = *res;
+        *res = r;
+        res->cam_cov = keep.cam_cov; res->cam_ldim = keep.cam_ldim; res->cam_cov_full = keep.cam_cov_full;
+        res->point_cov = keep.point_cov; res->point_valid = keep.point_valid; res->nc = keep.nc; res->reserved = keep.reserved;
+    }
+    OSFM_RETURN_IF(rc);
+    if (res->cam_ldim) for (int c = 0; c < C; ++c) res->cam_ldim[c] = L.cam_ldim[c];
+    if (res->cam_cov && C) memcpy(res->cam_cov, h.cam_cov.data(), (size_t)C * 36 * 8);
+    if (res->cam_cov_full && L.nc) memcpy(res->cam_cov_full, h.full.data(), (size_t)L.nc * L.nc * 8);
+    if (pdim && want_points) {
+        // per scene track in the caller's numbering: the problem's point -> the scene's track -> the caller's
+        const size_t T0 = sc->compacted ? (size_t)sc->T0 : (size_t)T;
+        std::vector<int32_t> track((size_t)std::max(M, 1)), orig;
+        if (M) OSFM_HIP_CHECK(hipMemcpyAsync(track.data(), P.point_track.ptr, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+        if (sc->compacted && T) {
+            orig.resize((size_t)T);
+            OSFM_HIP_CHECK(hipMemcpyAsync(orig.data(), sc->orig_t.ptr, (size_t)T * 4, hipMemcpyDeviceToHost, s));
+        }
+        OSFM_HIP_CHECK(hipStreamSynchronize(s));
+        if (res->point_cov) memset(res->point_cov, 0, T0 * 9 * 8);
+        if (res->point_valid) memset(res->point_valid, 0, T0);
+        for (int j = 0; j < M; ++j) {
+            const size_t t = sc->compacted ? (size_t)orig[track[j]] : (size_t)track[j];
+            if (res->point_cov) memcpy(res->point_cov + t * 9, h.point_cov.data() + (size_t)j * 9, 72);
+            if (res->point_valid) res->point_valid[t] = h.valid[j];
+        }
+    }
     return OSFM_OK;
 }
 

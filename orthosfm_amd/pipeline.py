@@ -384,6 +384,13 @@ class Result:
     initial_alignments: list = field(default_factory=list)      # one tk.Alignment per group (initial_alignment="tk")
     verification: str = "none"       # model of the geometric verification: "none", "fundamental" or "affine"
     resected_groups: list = field(default_factory=list)         # ordinals of the groups started from a resection
+    # reconstruct(..., uncertainty=True): ba.Covariance of the last global adjustment's problem and what is read off it
+    covariance: object = None
+    cam_cov: np.ndarray | None = None
+    point_cov: np.ndarray | None = None
+    point_valid: np.ndarray | None = None
+    point_sigma: np.ndarray | None = None
+    variance_factor: float | None = None
 
 
 def _problem(model, cams, const, width, height, points, xy, obs_cam, obs_pt):
@@ -759,7 +766,8 @@ def weak_group_action(tk_status, first_group, policy):
 def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2.0, off_perturb=0.01,
                         seed=7, timings=None, capture=(), max_groups=None, verbose=False, view_ids=None,
                         euler_dof=4, check_incremental=False, use_scene=True, initial_alignment="perturbed",
-                        alignments=None, local_solver="general", weak_group="raise", tk_options=None, resected=None):
+                        alignments=None, local_solver="general", weak_group="raise", tk_options=None, resected=None,
+                        uncertainty=None):
     """runPoseEstimation (reconstruct.cpp:174-295) on the track table.  initial_alignment: "perturbed" or "tk" (see
     the module docstring); with "tk", group_id is the group's ordinal, seed the sampler's seed, and the groups'
     tk.Alignment records are appended to `alignments` (a list, if given).  use_scene: the table lives on the device
@@ -772,7 +780,10 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
     without a supported model (weak_group_action) starts its aligned views from their global cameras and its new views
     from a resection against the scene's points (resect.resect / Scene.resect_view, stream_id = the group's ordinal);
     if a resection is not OK the group does what "raise" does.  The ordinals of the resected groups are appended to
-    `resected` (a list, if given) and counted in timings.resected_groups."""
+    `resected` (a list, if given) and counted in timings.resected_groups.  uncertainty: a dict (if given) that
+    receives, under "covariance", the ba.Covariance of the problem the last global adjustment solved, taken once
+    after it at the adjusted values (Scene.covariance / ba.covariance), with point_cov / point_valid per track of the
+    caller's table; nothing else changes."""
     if local_solver not in ("general", "small"):
         raise ValueError(f"local_solver {local_solver!r}: 'general' or 'small'")
     if weak_group not in WEAK_GROUP_POLICIES:
@@ -1054,6 +1065,8 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
         tm.global_ba_s += dt
         calls.append(BaCall("final", len(aligned), M, O, int(s.num_iterations), dt * 1e3, s.lm_loop_ms))
         cams[aligned] = scene.cameras()[1]
+        if uncertainty is not None:
+            uncertainty["covariance"] = scene.covariance(device=device)
         # the scene's state into the caller's table
         t0 = time.perf_counter()
         at, af, hp, pt = scene.download()
@@ -1130,6 +1143,16 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
             print(f"group {processed}/{len(groups)} {ids}: {len(aligned)} cameras, {tt.num_tracks} tracks, "
                   f"{int(tt.has_point.sum())} points")
     _global_ba(tt, model, cams, const, aligned, W, H, V, solve, "final", opt, tm)      # :281
+    if uncertainty is not None:
+        prob, tsel = _global_problem(tt, model, cams, const, aligned, W, H)
+        cov = B.covariance(prob, device=device)
+        # per track of the caller's table (a track outside the problem is invalid, zero)
+        rows = getattr(tt, "orig_track", np.arange(tt.alive_t.shape[0]))[tsel]
+        n_all = full_table.alive_t.shape[0]
+        pc, pv = np.zeros((n_all, 3, 3)), np.zeros(n_all, dtype=bool)
+        pc[rows], pv[rows] = cov.point_cov, cov.point_valid
+        cov.point_cov, cov.point_valid = pc, pv
+        uncertainty["covariance"] = cov
     full_table.write_back(tt)
     tm.pose_s = time.perf_counter() - t_pose
     return cams, aligned, groups, calls, captured
@@ -1140,17 +1163,22 @@ def _outlier_flags(points, has_point, device):
     return filters.outlier_track_flags(points, has_point, device)
 
 
-def _global_ba(tt, model, cams, const, aligned, W, H, V, solve, kind, opt, tm):
-    """runBundleAdjustment(alignedCameras, tracks, algorithm, true, false): every track
-    with a point is a parameter block, every feature of such a track whose view has a
-    camera a residual (bundle_adjustment.cpp:86-123); cameras and points updated in place."""
-    t0 = time.perf_counter()
+def _global_problem(tt, model, cams, const, aligned, W, H):
+    """The global adjustment's problem and the table rows of its points."""
     with_point = tt.alive_t & tt.has_point
     tsel = np.flatnonzero(with_point)
     slot = (np.cumsum(with_point) - 1).astype(np.int32)                  # track -> row of tsel
     obs_xy, obs_cam, obs_pt, _, _ = T.select_observations(tt.track_of, tt.cam_f, tt.live_f, tt.xy,
                                                           track_mask=with_point, track_slot=slot, track_offsets=tt.offsets)
-    prob = _problem(model, cams[aligned], const[aligned], W, H, tt.point[tsel], obs_xy, obs_cam, obs_pt)
+    return _problem(model, cams[aligned], const[aligned], W, H, tt.point[tsel], obs_xy, obs_cam, obs_pt), tsel
+
+
+def _global_ba(tt, model, cams, const, aligned, W, H, V, solve, kind, opt, tm):
+    """runBundleAdjustment(alignedCameras, tracks, algorithm, true, false): every track
+    with a point is a parameter block, every feature of such a track whose view has a
+    camera a residual (bundle_adjustment.cpp:86-123); cameras and points updated in place."""
+    t0 = time.perf_counter()
+    prob, tsel = _global_problem(tt, model, cams, const, aligned, W, H)
     tm.pose_host_s += time.perf_counter() - t0
     s, dt = solve(kind, prob, opt)
     tm.global_ba_s += dt
@@ -1164,27 +1192,37 @@ def _global_ba(tt, model, cams, const, aligned, W, H, V, solve, kind, opt, tm):
 def reconstruct(iset, solver=0, matcher="exhaustive", device=0, verify=True, rot_perturb_deg=2.0,
                 off_perturb=0.01, seed=7, capture=(), max_groups=None, verbose=False,
                 check_incremental=False, use_scene=True, initial_alignment="perturbed", local_solver="general",
-                weak_group="raise", tk_options=None, guided=False) -> Result:
+                weak_group="raise", tk_options=None, guided=False, uncertainty=False) -> Result:
     """orthosfm::reconstruct from the views' descriptors on: one wall clock over matching,
     track building, group ordering and the incremental pose estimation.
     solver 0: quaternion cameras (ORTHO_QUATERNION); 1..3: Euler cameras with that many
     free angle blocks (3 = ORTHO_EULER_ALL_DOF: phi, theta, roll and the offsets).
     verify, guided: match_and_build_tracks' (True, False or "affine"; guided matching of the verified pairs).  local_solver, weak_group, tk_options:
-    run_pose_estimation's."""
+    run_pose_estimation's.  uncertainty: after the last global adjustment, one ba.covariance / Scene.covariance call at the
+    adjusted values: Result.cam_cov (per aligned camera, join order), point_cov / point_valid / point_sigma (per track of
+    Result.tracks; point_sigma = sqrt(variance_factor * largest eigenvalue), NaN where the point is invalid) and
+    variance_factor.  Filtering on them is the caller's.  False: the function does exactly what it did without it."""
     tm = Timings()
     t_all = time.perf_counter()
     tt, info = match_and_build_tracks(iset, matcher, device, verify, tm, guided=guided)
     model = B.MODEL_QUATERNION if solver == 0 else B.MODEL_EULER
     alignments, resected = [], []
+    unc = {} if uncertainty else None
     cams, aligned, groups, calls, captured = run_pose_estimation(
         tt, iset, model, device, rot_perturb_deg, off_perturb, seed, tm, capture, max_groups, verbose,
         euler_dof=euler_dof_of_solver(solver), check_incremental=check_incremental, use_scene=use_scene,
         initial_alignment=initial_alignment, alignments=alignments, local_solver=local_solver,
-        weak_group=weak_group, tk_options=tk_options, resected=resected)
+        weak_group=weak_group, tk_options=tk_options, resected=resected, uncertainty=unc)
     join_background()            # inside the clock: the matcher's memory is back when the job is done
     tm.total_s = time.perf_counter() - t_all
     info.pop("match_stats", None)
-    return Result(cams, aligned, tt, groups, tm, calls, captured=captured, initial_alignments=alignments, resected_groups=resected, **info)
+    res = Result(cams, aligned, tt, groups, tm, calls, captured=captured, initial_alignments=alignments, resected_groups=resected, **info)
+    if unc:
+        cov = unc["covariance"]
+        res.covariance = cov
+        res.cam_cov, res.point_cov, res.point_valid = cov.cam_cov, cov.point_cov, cov.point_valid
+        res.variance_factor, res.point_sigma = cov.variance_factor, cov.point_sigma()
+    return res
 
 
 CAMERA_DISTANCE = 10.0                  # OrthoQuaternionCamera.cpp:70, OrthographicCamera.h:119

@@ -130,6 +130,17 @@ class Scene:
         capi.check(capi.lib.osfm_scene_global_adjustment(self._h_scene, C.byref(options), C.byref(s), C.byref(m), C.byref(o)))
         return s, m.value, o.value
 
+    def covariance(self, options=None, full: bool = False, skip=(), fill=None, **kw):
+        """osfm_scene_covariance: ba.covariance on the selection global_adjustment makes, bit for bit what the per-call
+        entry gives on that problem; cameras in join order, points per scene track in the caller's numbering (a track
+        outside the selection is invalid).  The scene is not changed.  Returns a ba.Covariance."""
+        from . import ba
+        o = options if options is not None else ba.cov_options(**kw)
+        n = C.c_int32()
+        capi.check(capi.lib.osfm_scene_get_cameras(self._h_scene, 0, None, None, C.byref(n)))
+        return ba._covariance_call(lambda oo, r: capi.lib.osfm_scene_covariance(self._h_scene, C.byref(oo), C.byref(r)),
+                                   n.value, self.num_tracks, 6 * n.value, o, full, skip, fill)
+
     def filter_outliers(self) -> int:
         k = C.c_int32()
         capi.check(capi.lib.osfm_scene_filter_outliers(self._h_scene, None, C.byref(k)))
