@@ -44,7 +44,8 @@ OSFM_API const char *osfm_last_error(void);
  * nothing that a caller built against 102 reads or writes has changed.  osfm_match_options has since got
  * ransac_model / ransac_refit appended, and the library READS that struct: the three entries that take it are bound
  * under new symbol names by this header (see below it), and the symbols a caller built against the earlier header
- * binds keep the earlier, shorter layout.  Such a caller still runs correctly, so the version is still 102. */
+ * binds keep the earlier, shorter layout.  Such a caller still runs correctly, so the version is still 102.  The
+ * consensus filter (osfm_ba_consensus, osfm_scene_filter_consensus and their structs) is new entries only. */
 #define OSFM_ABI_VERSION 102
 OSFM_API int osfm_version(void);
 /* Number of visible HIP devices (0 when there is none). */
@@ -963,6 +964,74 @@ OSFM_API int osfm_scene_resect_view(osfm_scene *s, int32_t view, const osfm_rese
  * err and point_valid may be NULL. */
 OSFM_API int osfm_filter_reprojection(const osfm_ba_problem *p, int device,
     double max_error, uint8_t *obs_keep, uint8_t *point_valid, double *err);
+
+/* ---- per-track consensus triangulation: drop single wrong observations, keep the track ----
+ *
+ * Not in the reference, and opt-in.  filterTracksWithReprojectionError above intersects ALL rays of a track, the wrong
+ * one included, and judges every feature against that pulled point; and it judges only tracks that every camera
+ * sees.  Here every track of two or more observations is tested under the problem's cameras (DESIGN.md section 3.5b;
+ * tests/consensus_restatement.py is the definition):
+ *   sample     all n observations when n <= max_sample, else the observations floor(i n / max_sample)
+ *   hypotheses every pair a < b of the sample, in lexicographic order: the midpoint of the common perpendicular of
+ *              the two rays (skipped when 1 - (d_a . d_b)^2 <= 1e-12), scored against all n observations through
+ *              the cameras' affine projections: inlier when the pixel distance is < max_error.  The winner has the
+ *              most inliers, then the smallest sum of squared inlier errors, then the lowest index
+ *   refit      refit_rounds times: the ray intersection of osfm_ba_triangulate over the mask, the errors of
+ *              osfm_ba_reprojection_errors at it, the new mask err < max_error; a round that would fit fewer than two
+ *              observations ends the loop.  refit_rounds == 0: the winner's midpoint and mask stand
+ *   verdict    all n kept: CLEAN; at least min_support kept: REPAIRED; else UNSUPPORTED (every keep flag 0)
+ * Tracks of fewer than two observations are UNTESTED, tracks without a valid pair DEGENERATE; both keep every
+ * observation.  Results repeat to the bit and do not depend on the order of the tracks. */
+enum {
+    OSFM_CONSENSUS_UNTESTED = 0,
+    OSFM_CONSENSUS_CLEAN = 1,
+    OSFM_CONSENSUS_REPAIRED = 2,
+    OSFM_CONSENSUS_UNSUPPORTED = 3,
+    OSFM_CONSENSUS_DEGENERATE = 4
+};
+#define OSFM_CONSENSUS_MAX_REFIT_ROUNDS 16
+
+typedef struct osfm_consensus_options {
+    double max_error;             /* 1.5 px; > 0 */
+    int32_t min_support;          /* 3; >= 2 */
+    int32_t max_sample;           /* 16; 2..16 */
+    int32_t refit_rounds;         /* 2; 0..OSFM_CONSENSUS_MAX_REFIT_ROUNDS */
+    int32_t device;               /* osfm_ba_consensus only (a scene has its own) */
+} osfm_consensus_options;
+OSFM_API void osfm_consensus_options_default(osfm_consensus_options *opts);
+
+/* how the kernels divide the work (tests place their sizes around these) */
+typedef struct osfm_consensus_limits {
+    int32_t short_length;         /* tracks of at most this many observations take the eight-lane path */
+    int32_t short_tracks;         /* tracks per workgroup there */
+    int32_t long_tracks;          /* tracks per workgroup of the wave-per-track path */
+    int32_t max_sample;           /* the sample cap's upper limit */
+} osfm_consensus_limits;
+OSFM_API void osfm_consensus_get_limits(osfm_consensus_limits *limits);
+
+typedef struct osfm_consensus_stats {
+    int64_t tracks_tested;        /* two or more observations */
+    int64_t tracks_clean, tracks_repaired, tracks_unsupported, tracks_degenerate;     /* sum: tracks_tested */
+    int64_t tracks_unsettled;     /* the last two masks of the refit differ */
+    int64_t obs_tested;           /* observations of the tested tracks */
+    int64_t obs_dropped;          /* keep flags cleared */
+    int64_t hypotheses_scored;    /* pairs that were not skipped */
+    double device_ms;
+} osfm_consensus_stats;
+
+/* p as for osfm_ba_solve; nothing of it is written.  opts NULL: the defaults on device 0.  Every output may be NULL:
+ * obs_keep [num_observations], track_status [num_points], points_out [num_points][4] (the consensus point of CLEAN and
+ * REPAIRED tracks, the input point of every other), point_valid [num_points] (1: CLEAN or REPAIRED), obs_err
+ * [num_observations] (the reprojection errors at points_out).  OSFM_E_ARG: a null problem or array, options out of
+ * range. */
+OSFM_API int osfm_ba_consensus(const osfm_ba_problem *p, const osfm_consensus_options *opts, uint8_t *obs_keep,
+    int32_t *track_status, double *points_out, uint8_t *point_valid, double *obs_err, osfm_consensus_stats *stats);
+/* The same over the scene's aligned cameras and every alive track with two or more live features in aligned views,
+ * permanent: dropped features lose their flag; a track dies when its kept aligned features plus its live features in
+ * views without a camera number fewer than two (the reference's newTrack.size() > 1); REPAIRED tracks that have a
+ * point take the consensus point.  Everything else is untouched.  Equal, bit for bit, to osfm_ba_consensus on the
+ * same features flattened in table order.  stats may be NULL. */
+OSFM_API int osfm_scene_filter_consensus(osfm_scene *s, const osfm_consensus_options *opts, osfm_consensus_stats *stats);
 
 /* ---- track building ---- */
 

@@ -299,6 +299,31 @@ class BaCovResult(C.Structure):
 
 BA_COV_MAX_UNKNOWNS = 8192
 
+
+class ConsensusOptions(C.Structure):
+    """osfm_consensus_options."""
+    _fields_ = [("max_error", C.c_double), ("min_support", C.c_int32), ("max_sample", C.c_int32),
+                ("refit_rounds", C.c_int32), ("device", C.c_int32)]
+
+
+class ConsensusLimits(C.Structure):
+    """osfm_consensus_limits."""
+    _fields_ = [(n, C.c_int32) for n in ("short_length", "short_tracks", "long_tracks", "max_sample")]
+
+
+class ConsensusStats(C.Structure):
+    """osfm_consensus_stats."""
+    COUNTERS = ("tracks_tested", "tracks_clean", "tracks_repaired", "tracks_unsupported", "tracks_degenerate",
+                "tracks_unsettled", "obs_tested", "obs_dropped", "hypotheses_scored")
+    _fields_ = [(n, C.c_int64) for n in COUNTERS] + [("device_ms", C.c_double)]
+
+    def counters(self) -> dict:
+        return {n: int(getattr(self, n)) for n in self.COUNTERS}
+
+
+CONSENSUS_UNTESTED, CONSENSUS_CLEAN, CONSENSUS_REPAIRED, CONSENSUS_UNSUPPORTED, CONSENSUS_DEGENERATE = 0, 1, 2, 3, 4
+CONSENSUS_MAX_REFIT_ROUNDS = 16
+
 # every symbol include/osfm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "osfm_last_error", "osfm_version", "osfm_device_count", "osfm_device_memory", "osfm_library_memory", "osfm_trim_device_memory", "osfm_ransac_selfcheck", "osfm_ba_debug_chol_trace", "osfm_ba_debug_flow_spin_limit", "osfm_ba_debug_order",
@@ -313,6 +338,7 @@ EXPORTS = [
     "osfm_ba_options_default", "osfm_ba_small_limits", "osfm_ba_solve", "osfm_ba_reprojection_errors",
     "osfm_ba_triangulate", "osfm_ba_cov_options_default", "osfm_ba_covariance", "osfm_scene_covariance",
     "osfm_nn_distances", "osfm_filter_outlier_tracks", "osfm_filter_reprojection",
+    "osfm_consensus_options_default", "osfm_consensus_get_limits", "osfm_ba_consensus", "osfm_scene_filter_consensus",
     "osfm_scene_create", "osfm_scene_destroy", "osfm_scene_set_flags", "osfm_scene_align_views", "osfm_scene_set_cameras", "osfm_scene_get_cameras",
     "osfm_scene_triangulate", "osfm_scene_filter_reprojection", "osfm_scene_local_adjustment", "osfm_scene_global_adjustment",
     "osfm_scene_filter_outliers", "osfm_scene_download",
@@ -399,6 +425,12 @@ lib.osfm_match_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C
 lib.osfm_ba_cov_options_default.argtypes = [C.POINTER(BaCovOptions)]
 lib.osfm_ba_covariance.argtypes = [C.c_void_p, C.POINTER(BaCovOptions), C.POINTER(BaCovResult)]
 lib.osfm_scene_covariance.argtypes = [C.c_void_p, C.POINTER(BaCovOptions), C.POINTER(BaCovResult)]
+lib.osfm_consensus_options_default.restype = None
+lib.osfm_consensus_options_default.argtypes = [C.POINTER(ConsensusOptions)]
+lib.osfm_consensus_get_limits.restype = None
+lib.osfm_consensus_get_limits.argtypes = [C.POINTER(ConsensusLimits)]
+lib.osfm_ba_consensus.argtypes = [C.c_void_p, C.POINTER(ConsensusOptions)] + [C.c_void_p] * 5 + [C.POINTER(ConsensusStats)]
+lib.osfm_scene_filter_consensus.argtypes = [C.c_void_p, C.POINTER(ConsensusOptions), C.POINTER(ConsensusStats)]
 lib.osfm_ba_debug_cholesky_solve.restype = C.c_int
 lib.osfm_ba_debug_cholesky_solve.argtypes = [C.c_int, C.c_int, _f64p, _f64p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, _f64p, _i32p, _i32p]
@@ -494,6 +526,23 @@ def guided_limits():
     a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
     check(lib.osfm_guided_limits(C.byref(a), C.byref(b), C.byref(c)))
     return a.value, b.value, c.value
+
+
+def default_consensus_options(**kw) -> ConsensusOptions:
+    """osfm_consensus_options_default with the given fields replaced."""
+    o = ConsensusOptions()
+    lib.osfm_consensus_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"osfm_consensus_options has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def consensus_limits() -> ConsensusLimits:
+    l = ConsensusLimits()
+    lib.osfm_consensus_get_limits(C.byref(l))
+    return l
 
 
 def default_sift_options() -> SiftOptions:

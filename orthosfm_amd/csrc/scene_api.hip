@@ -31,6 +31,7 @@
 
 #include "ba_cov.h"
 #include "ba_solve.h"
+#include "consensus_kernels.h"
 #include "resect_kernels.h"
 #include "tk_kernels.h"
 
@@ -107,7 +108,7 @@ __global__ void scene_touch_kernel(int64_t F, const int32_t *__restrict__ view, 
 }
 
 // tflag[t] from the counts / masks of an operation (see the callers), with the scan's extra last entry
-enum { kFlagCountPositive = 0, kFlagCountEquals = 1, kFlagAliveWithPoint = 2, kFlagAlive = 3 };
+enum { kFlagCountPositive = 0, kFlagCountEquals = 1, kFlagAliveWithPoint = 2, kFlagAlive = 3, kFlagCountAtLeast = 4 };
 __global__ void scene_track_flag_kernel(int T, int mode, int n, const int32_t *__restrict__ cnt, const uint8_t *__restrict__ alive_t,
     const uint8_t *__restrict__ has_point, int32_t *__restrict__ tflag)
 {
@@ -118,6 +119,7 @@ __global__ void scene_track_flag_kernel(int T, int mode, int n, const int32_t *_
     if (mode == kFlagCountPositive) v = cnt[t] > 0;
     else if (mode == kFlagCountEquals) v = cnt[t] == n;
     else if (mode == kFlagAliveWithPoint) v = alive_t[t] && has_point[t];
+    else if (mode == kFlagCountAtLeast) v = cnt[t] >= n;
     else v = alive_t[t];
     tflag[t] = v;
 }
@@ -504,6 +506,29 @@ int reprojection_filter(osfm_scene *sc, int n, const int32_t *views, const doubl
     return OSFM_OK;
 }
 
+// the consensus filter made permanent, per tested track (slot j of the compacted problem): dropped features lose
+// their flag; the track dies when what it keeps under the cameras plus what lives outside them is fewer than two
+// features (the reference's newTrack.size() > 1); a REPAIRED track that has a point takes the consensus point
+__global__ void scene_consensus_apply_kernel(int T, const int32_t *__restrict__ offsets, const int32_t *__restrict__ sel,
+    const int32_t *__restrict__ scan, const int32_t *__restrict__ tflag, const int32_t *__restrict__ tslot,
+    const uint8_t *__restrict__ keep, const int32_t *__restrict__ status, const double *__restrict__ points_out,
+    const int32_t *__restrict__ cnt_set, const int32_t *__restrict__ cnt_live, uint8_t *__restrict__ alive_f,
+    uint8_t *__restrict__ alive_t, const uint8_t *__restrict__ has_point, double *__restrict__ point)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T || !tflag[t]) return;
+    const int j = tslot[t];
+    int kept = 0;
+    for (int f = offsets[t]; f < offsets[t + 1]; ++f) {
+        if (!sel[f]) continue;
+        if (keep[scan[f]]) ++kept;
+        else alive_f[f] = 0;
+    }
+    if (kept + (cnt_live[t] - cnt_set[t]) < 2) { alive_t[t] = 0; return; }
+    if (status[j] == OSFM_CONSENSUS_REPAIRED && has_point[t])
+        for (int i = 0; i < 4; ++i) point[4 * (size_t)t + i] = points_out[4 * (size_t)j + i];
+}
+
 // ---- compaction: the alive features of the alive tracks, in order ----
 __global__ void scene_compact_features_kernel(int64_t F, const int32_t *__restrict__ sel, const int32_t *__restrict__ scan,
     const int32_t *__restrict__ tslot, const int32_t *__restrict__ view, const double2 *__restrict__ xy,
@@ -881,6 +906,71 @@ int osfm_scene_filter_reprojection(osfm_scene *sc, double max_error)
     if (C == 0 || sc->T == 0) return OSFM_OK;
     int nsel = 0;
     return reprojection_filter(sc, C, sc->aligned.data(), sc->h_cams.data(), sc->h_const.data(), max_error, true, sg.s, &nsel);
+}
+
+int osfm_scene_filter_consensus(osfm_scene *sc, const osfm_consensus_options *opts, osfm_consensus_stats *stats)
+{
+    if (!sc) { set_error("scene_filter_consensus: null scene"); return OSFM_E_ARG; }
+    osfm_consensus_options o;
+    osfm_consensus_options_default(&o);
+    if (opts) o = *opts;
+    OSFM_RETURN_IF(consensus_check_options(&o, "scene_filter_consensus"));
+    if (stats) memset(stats, 0, sizeof(*stats));
+    std::lock_guard<std::mutex> lock(sc->mu);
+    OSFM_RETURN_IF(select_device(sc->device));
+    StreamLease sg;
+    OSFM_RETURN_IF(sg.acquire());
+    hipStream_t s = sg.s;
+    const int C = (int)sc->aligned.size(), T = sc->T;
+    const int64_t F = sc->F;
+    if (C == 0 || T == 0) return OSFM_OK;
+    int32_t *in_set = sc->aux_f.as<int32_t>(), *sel = in_set + (F + 1), *scan2 = sel + (F + 1);
+    int32_t *live = sc->sel.as<int32_t>(), *scan = sc->scan.as<int32_t>();
+    int32_t *cnt_set = sc->cnt.as<int32_t>(), *tflag = sc->tflag.as<int32_t>(), *cnt_live = sc->aux_t.as<int32_t>();
+    uint8_t *tmask = sc->aux_t2.as<uint8_t>();
+    const int32_t *cam_map = sc->cam_of_view.as<int32_t>();
+    const dim3 gF(blocks_for(F + 1)), gT(blocks_for(T + 1)), b(kThreads);
+    // live features under the aligned cameras and all live features, per track
+    hipLaunchKernelGGL(scene_select_kernel, gF, b, 0, s, F, sc->feat_view.as<int32_t>(), sc->track_of.as<int32_t>(),
+        sc->alive_f.as<uint8_t>(), sc->alive_t.as<uint8_t>(), cam_map, nullptr, in_set);
+    OSFM_RETURN_IF(exclusive_scan(sc, in_set, scan, F + 1, s));
+    hipLaunchKernelGGL(scene_track_count_kernel, gT, b, 0, s, T, sc->offsets.as<int32_t>(), scan, cnt_set);
+    hipLaunchKernelGGL(scene_select_kernel, gF, b, 0, s, F, sc->feat_view.as<int32_t>(), sc->track_of.as<int32_t>(),
+        sc->alive_f.as<uint8_t>(), sc->alive_t.as<uint8_t>(), nullptr, nullptr, live);
+    OSFM_RETURN_IF(exclusive_scan(sc, live, scan, F + 1, s));
+    hipLaunchKernelGGL(scene_track_count_kernel, gT, b, 0, s, T, sc->offsets.as<int32_t>(), scan, cnt_live);
+    // the tested tracks: two or more of the former; their features in table order are the problem's observations
+    hipLaunchKernelGGL(scene_track_flag_kernel, gT, b, 0, s, T, (int)kFlagCountAtLeast, 2, cnt_set, nullptr, nullptr, tflag);
+    hipLaunchKernelGGL(scene_to_byte_kernel, gT, b, 0, s, T, tflag, tmask);
+    hipLaunchKernelGGL(scene_select_kernel, gF, b, 0, s, F, sc->feat_view.as<int32_t>(), sc->track_of.as<int32_t>(),
+        sc->alive_f.as<uint8_t>(), sc->alive_t.as<uint8_t>(), cam_map, tmask, sel);
+    OSFM_RETURN_IF(exclusive_scan(sc, sel, scan2, F + 1, s));
+    OSFM_RETURN_IF(exclusive_scan(sc, tflag, sc->tslot.as<int32_t>(), (int64_t)T + 1, s));
+    int O1 = 0, M1 = 0;
+    OSFM_RETURN_IF(read_totals2(scan2, F, sc->tslot.as<int32_t>(), T, s, &O1, &M1));
+    if (M1 == 0) return OSFM_OK;
+    Compact P;
+    Layout L;
+    OSFM_RETURN_IF(build_problem(sc, sel, scan2, O1, tflag, sc->point.as<double>(), C, nullptr, sc->cams.as<double>(), sc->h_const.data(),
+        sc->aligned.data(), cam_map, 1.0, 3, &L, s, &P, M1));
+    ConsensusBuffers B;
+    OSFM_RETURN_IF(B.alloc(M1, O1));
+    OSFM_HIP_CHECK(hipEventRecord(sg.ev[0].a, s));
+    OSFM_RETURN_IF(consensus_run(P.D.dev, o, B.out(), s));
+    OSFM_HIP_CHECK(hipEventRecord(sg.ev[0].b, s));
+    hipLaunchKernelGGL(scene_consensus_apply_kernel, gT, b, 0, s, T, sc->offsets.as<int32_t>(), sel, scan2, tflag, sc->tslot.as<int32_t>(),
+        B.keep.as<uint8_t>(), B.status.as<int32_t>(), B.points.as<double>(), cnt_set, cnt_live, sc->alive_f.as<uint8_t>(),
+        sc->alive_t.as<uint8_t>(), sc->has_point.as<uint8_t>(), sc->point.as<double>());
+    OSFM_HIP_CHECK(hipGetLastError());
+    unsigned long long counters[kCsCounters];
+    OSFM_HIP_CHECK(hipMemcpyAsync(counters, B.counters.ptr, sizeof(counters), hipMemcpyDeviceToHost, s));
+    OSFM_HIP_CHECK(hipStreamSynchronize(s));
+    if (stats) {
+        float ms = 0.0f;
+        OSFM_HIP_CHECK(hipEventElapsedTime(&ms, sg.ev[0].a, sg.ev[0].b));
+        consensus_fill_stats(counters, ms, stats);
+    }
+    return OSFM_OK;
 }
 
 int osfm_scene_local_adjustment(osfm_scene *sc, int n, const int32_t *views, double *params, const uint8_t *cam_const,

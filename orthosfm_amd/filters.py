@@ -22,6 +22,34 @@ from .ba import Track, _flatten
 MAX_ALLOWED_REPROJECTION_ERROR = 1.5     # pixels, outlier_filtering.cpp:140
 
 
+class Consensus:
+    """What filters.consensus returns: keep (O,) bool, status (M,) int32 (capi.CONSENSUS_*), points (M, 4) -- the
+    consensus point of CLEAN and REPAIRED tracks, the input point of every other --, valid (M,) bool, err (O,) the
+    reprojection errors at points, stats (capi.ConsensusStats)."""
+
+    def __init__(self, keep, status, points, valid, err, stats):
+        self.keep, self.status, self.points, self.valid, self.err, self.stats = keep, status, points, valid, err, stats
+
+
+def consensus(problem, **opts) -> Consensus:
+    """osfm_ba_consensus: per track of `problem` (a ba.FlatProblem or anything with its struct()), which observations
+    agree on one point under the problem's cameras.  Not in the reference: its reprojection filter intersects all
+    rays of a track, the wrong one included.  opts: fields of osfm_consensus_options (max_error, min_support,
+    max_sample, refit_rounds, device).  The problem is not changed."""
+    st = problem.struct()
+    M, O = int(st.num_points), int(st.num_observations)
+    o = capi.default_consensus_options(**opts)
+    keep = np.zeros(max(O, 1), dtype=np.uint8)
+    status = np.zeros(max(M, 1), dtype=np.int32)
+    points = np.zeros((max(M, 1), 4))
+    valid = np.zeros(max(M, 1), dtype=np.uint8)
+    err = np.zeros(max(O, 1))
+    stats = capi.ConsensusStats()
+    capi.check(capi.lib.osfm_ba_consensus(C.byref(st), C.byref(o), keep.ctypes.data, status.ctypes.data, points.ctypes.data,
+                                          valid.ctypes.data, err.ctypes.data, C.byref(stats)))
+    return Consensus(keep[:O].astype(bool), status[:M], points[:M], valid[:M].astype(bool), err[:O], stats)
+
+
 def nearest_neighbour_distance(points, device: int = 0) -> np.ndarray:
     """points: (n, 4) homogeneous; returns the (n,) distances."""
     pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 4)

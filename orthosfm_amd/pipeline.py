@@ -349,6 +349,7 @@ class Timings:
     triangulate_s: float = 0.0
     global_ba_s: float = 0.0
     outlier_filter_s: float = 0.0
+    consensus_filter_s: float = 0.0   # track_filter="consensus": the per-track consensus filter behind the global adjustments
     pose_host_s: float = 0.0
     pose_s: float = 0.0
     total_s: float = 0.0
@@ -391,6 +392,8 @@ class Result:
     point_valid: np.ndarray | None = None
     point_sigma: np.ndarray | None = None
     variance_factor: float | None = None
+    # track_filter="consensus": the counters of osfm_consensus_stats summed over the filter's calls, and "calls"
+    consensus_stats: dict = field(default_factory=dict)
 
 
 def _problem(model, cams, const, width, height, points, xy, obs_cam, obs_pt):
@@ -750,6 +753,9 @@ def join_background():
 WEAK_GROUP_POLICIES = ("raise", "resect")
 
 
+TRACK_FILTERS = ("reference", "consensus")
+
+
 def weak_group_action(tk_status, first_group, policy):
     """What a camera group does with the status of its Tomasi-Kanade alignment: "tk" (start from the model the
     alignment returned: a supported one, or the fallback's), "resect" (place its new views against the scene's points)
@@ -767,7 +773,7 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
                         seed=7, timings=None, capture=(), max_groups=None, verbose=False, view_ids=None,
                         euler_dof=4, check_incremental=False, use_scene=True, initial_alignment="perturbed",
                         alignments=None, local_solver="general", weak_group="raise", tk_options=None, resected=None,
-                        uncertainty=None):
+                        uncertainty=None, track_filter="reference", consensus_stats=None):
     """runPoseEstimation (reconstruct.cpp:174-295) on the track table.  initial_alignment: "perturbed" or "tk" (see
     the module docstring); with "tk", group_id is the group's ordinal, seed the sampler's seed, and the groups'
     tk.Alignment records are appended to `alignments` (a list, if given).  use_scene: the table lives on the device
@@ -783,7 +789,23 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
     `resected` (a list, if given) and counted in timings.resected_groups.  uncertainty: a dict (if given) that
     receives, under "covariance", the ba.Covariance of the problem the last global adjustment solved, taken once
     after it at the adjusted values (Scene.covariance / ba.covariance), with point_cov / point_valid per track of the
-    caller's table; nothing else changes."""
+    caller's table; nothing else changes.  track_filter: "reference" (what the reference does: behind a global
+    adjustment its reprojection filter over all aligned cameras, which judges only tracks that every camera sees) or
+    "consensus": the per-track consensus filter (filters.consensus / Scene.filter_consensus) over all aligned cameras
+    takes that filter's place, and runs once more after the final adjustment, followed by one more global adjustment
+    if it dropped anything.  Its counters are summed into `consensus_stats` (a dict, if given)."""
+    if track_filter not in TRACK_FILTERS:
+        raise ValueError(f"track_filter {track_filter!r}: 'reference' or 'consensus'")
+    use_consensus = track_filter == "consensus"
+    cstats = consensus_stats if consensus_stats is not None else {}
+
+    def book_consensus(st, dt):
+        tm.consensus_filter_s += dt
+        cstats["calls"] = cstats.get("calls", 0) + 1
+        for k, v in st.counters().items():
+            cstats[k] = cstats.get(k, 0) + v
+        return st.obs_dropped
+
     if local_solver not in ("general", "small"):
         raise ValueError(f"local_solver {local_solver!r}: 'general' or 'small'")
     if weak_group not in WEAK_GROUP_POLICIES:
@@ -1006,6 +1028,27 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
         tm.local_filter_s += time.perf_counter() - t0
         return idx[sel]
 
+    def consensus_filter():
+        """Scene.filter_consensus through the per-call entry: every live track with two or more live features in
+        aligned views, flattened in table order under the aligned cameras; dropped features lose their flag, a track
+        left with fewer than two features (what it keeps plus what lives in views without a camera) goes, REPAIRED
+        tracks that have a point take the consensus point.  Returns what it dropped."""
+        from . import filters
+        t0 = time.perf_counter()
+        idx = np.flatnonzero(tt.live_f & (tt.cam_f >= 0))
+        uniq, first, cnt, run = _runs(tt.track_of[idx])
+        tested = cnt >= 2
+        fi, fu = idx[tested[run]], uniq[tested]
+        prob = _problem(model, cams[aligned], const[aligned], W, H, tt.point[fu].copy(), tt.xy[fi], tt.cam_f[fi],
+                        np.repeat(np.arange(fu.shape[0], dtype=np.int32), cnt[tested]))
+        res = filters.consensus(prob, device=device)
+        kept = np.add.reduceat(res.keep.astype(np.int64), np.concatenate([[0], np.cumsum(cnt[tested])[:-1]])) if fu.size else np.zeros(0, np.int64)
+        left = kept + tt.alive_lengths()[fu] - cnt[tested]
+        take = (left >= 2) & (res.status == capi.CONSENSUS_REPAIRED) & tt.has_point[fu]
+        tt.point[fu[take]] = res.points[take]
+        tt.kill(tracks=fu[left < 2], features=fi[~res.keep])
+        return book_consensus(res.stats, time.perf_counter() - t0)
+
     if scene is not None:
         # ---- the loop on the device-resident scene ----------------------------------------------------------
         tri_full = True
@@ -1055,8 +1098,11 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
                 scene.filter_outliers()
                 tm.outlier_filter_s += time.perf_counter() - t0
                 t0 = time.perf_counter()
-                scene.filter_reprojection(MAX_REPROJECTION_ERROR)      # no track seen by every camera: nothing is judged
-                tm.local_filter_s += time.perf_counter() - t0
+                if use_consensus:
+                    book_consensus(scene.filter_consensus(), time.perf_counter() - t0)
+                else:
+                    scene.filter_reprojection(MAX_REPROJECTION_ERROR)      # no track seen by every camera: nothing is judged
+                    tm.local_filter_s += time.perf_counter() - t0
             if verbose:
                 print(f"group {processed}/{len(groups)} {ids}: {len(aligned)} cameras")
         t0 = time.perf_counter()
@@ -1065,6 +1111,16 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
         tm.global_ba_s += dt
         calls.append(BaCall("final", len(aligned), M, O, int(s.num_iterations), dt * 1e3, s.lm_loop_ms))
         cams[aligned] = scene.cameras()[1]
+        if use_consensus:
+            t0 = time.perf_counter()
+            st = scene.filter_consensus()
+            if book_consensus(st, time.perf_counter() - t0):
+                t0 = time.perf_counter()
+                s, M, O = scene.global_adjustment(opt)
+                dt = time.perf_counter() - t0
+                tm.global_ba_s += dt
+                calls.append(BaCall("final", len(aligned), M, O, int(s.num_iterations), dt * 1e3, s.lm_loop_ms))
+                cams[aligned] = scene.cameras()[1]
         if uncertainty is not None:
             uncertainty["covariance"] = scene.covariance(device=device)
         # the scene's state into the caller's table
@@ -1132,7 +1188,9 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
                 keep, _ = _outlier_flags(tt.point[at], tt.has_point[at], device)
                 tt.kill(tracks=at[~keep])
                 tm.outlier_filter_s += time.perf_counter() - t0
-                if len(aligned) <= int(tt.alive_lengths().max(initial=0)):
+                if use_consensus:
+                    consensus_filter()
+                elif len(aligned) <= int(tt.alive_lengths().max(initial=0)):
                     reprojection_filter(list(aligned), cams[aligned], const[aligned], permanent=True)
                 # drop what the filters have cleared once it is most of the table
                 t0 = time.perf_counter()
@@ -1143,6 +1201,8 @@ def run_pose_estimation(tt: TrackTable, iset, model, device=0, rot_perturb_deg=2
             print(f"group {processed}/{len(groups)} {ids}: {len(aligned)} cameras, {tt.num_tracks} tracks, "
                   f"{int(tt.has_point.sum())} points")
     _global_ba(tt, model, cams, const, aligned, W, H, V, solve, "final", opt, tm)      # :281
+    if use_consensus and consensus_filter():
+        _global_ba(tt, model, cams, const, aligned, W, H, V, solve, "final", opt, tm)
     if uncertainty is not None:
         prob, tsel = _global_problem(tt, model, cams, const, aligned, W, H)
         cov = B.covariance(prob, device=device)
@@ -1192,7 +1252,7 @@ def _global_ba(tt, model, cams, const, aligned, W, H, V, solve, kind, opt, tm):
 def reconstruct(iset, solver=0, matcher="exhaustive", device=0, verify=True, rot_perturb_deg=2.0,
                 off_perturb=0.01, seed=7, capture=(), max_groups=None, verbose=False,
                 check_incremental=False, use_scene=True, initial_alignment="perturbed", local_solver="general",
-                weak_group="raise", tk_options=None, guided=False, uncertainty=False) -> Result:
+                weak_group="raise", tk_options=None, guided=False, uncertainty=False, track_filter="reference") -> Result:
     """orthosfm::reconstruct from the views' descriptors on: one wall clock over matching,
     track building, group ordering and the incremental pose estimation.
     solver 0: quaternion cameras (ORTHO_QUATERNION); 1..3: Euler cameras with that many
@@ -1201,22 +1261,27 @@ def reconstruct(iset, solver=0, matcher="exhaustive", device=0, verify=True, rot
     run_pose_estimation's.  uncertainty: after the last global adjustment, one ba.covariance / Scene.covariance call at the
     adjusted values: Result.cam_cov (per aligned camera, join order), point_cov / point_valid / point_sigma (per track of
     Result.tracks; point_sigma = sqrt(variance_factor * largest eigenvalue), NaN where the point is invalid) and
-    variance_factor.  Filtering on them is the caller's.  False: the function does exactly what it did without it."""
+    variance_factor.  Filtering on them is the caller's.  False: the function does exactly what it did without it.
+    track_filter: run_pose_estimation's ("reference": exactly what it did without it; "consensus": the per-track
+    consensus filter behind every global adjustment, its summed counters in Result.consensus_stats)."""
     tm = Timings()
     t_all = time.perf_counter()
     tt, info = match_and_build_tracks(iset, matcher, device, verify, tm, guided=guided)
     model = B.MODEL_QUATERNION if solver == 0 else B.MODEL_EULER
     alignments, resected = [], []
     unc = {} if uncertainty else None
+    cstats = {}
     cams, aligned, groups, calls, captured = run_pose_estimation(
         tt, iset, model, device, rot_perturb_deg, off_perturb, seed, tm, capture, max_groups, verbose,
         euler_dof=euler_dof_of_solver(solver), check_incremental=check_incremental, use_scene=use_scene,
         initial_alignment=initial_alignment, alignments=alignments, local_solver=local_solver,
-        weak_group=weak_group, tk_options=tk_options, resected=resected, uncertainty=unc)
+        weak_group=weak_group, tk_options=tk_options, resected=resected, uncertainty=unc, track_filter=track_filter,
+        consensus_stats=cstats)
     join_background()            # inside the clock: the matcher's memory is back when the job is done
     tm.total_s = time.perf_counter() - t_all
     info.pop("match_stats", None)
-    res = Result(cams, aligned, tt, groups, tm, calls, captured=captured, initial_alignments=alignments, resected_groups=resected, **info)
+    res = Result(cams, aligned, tt, groups, tm, calls, captured=captured, initial_alignments=alignments, resected_groups=resected,
+                 consensus_stats=cstats, **info)
     if unc:
         cov = unc["covariance"]
         res.covariance = cov

@@ -81,6 +81,15 @@ class Scene:
     def filter_reprojection(self, max_error: float):
         capi.check(capi.lib.osfm_scene_filter_reprojection(self._h_scene, C.c_double(max_error)))
 
+    def filter_consensus(self, **opts):
+        """osfm_scene_filter_consensus: the per-track consensus triangulation (filters.consensus) over the aligned
+        cameras and every live track with two or more live features in aligned views, permanent.  opts: fields of
+        osfm_consensus_options.  Returns the statistics (capi.ConsensusStats)."""
+        o = capi.default_consensus_options(**opts)
+        st = capi.ConsensusStats()
+        capi.check(capi.lib.osfm_scene_filter_consensus(self._h_scene, C.byref(o), C.byref(st)))
+        return st
+
     def local_adjustment(self, views, params, cam_const, max_error: float, options):
         """params is updated in place; returns (summary, points, observations)."""
         v = np.ascontiguousarray(views, dtype=np.int32)
