@@ -45,7 +45,8 @@ OSFM_API const char *osfm_last_error(void);
  * ransac_model / ransac_refit appended, and the library READS that struct: the three entries that take it are bound
  * under new symbol names by this header (see below it), and the symbols a caller built against the earlier header
  * binds keep the earlier, shorter layout.  Such a caller still runs correctly, so the version is still 102.  The
- * consensus filter (osfm_ba_consensus, osfm_scene_filter_consensus and their structs) is new entries only. */
+ * consensus filter (osfm_ba_consensus, osfm_scene_filter_consensus and their structs) is new entries only, and so
+ * is the observation refinement (osfm_refine_* and its structs). */
 #define OSFM_ABI_VERSION 102
 OSFM_API int osfm_version(void);
 /* Number of visible HIP devices (0 when there is none). */
@@ -1526,6 +1527,78 @@ typedef struct osfm_view_bank {
 OSFM_API int osfm_match_debug_view_bank(osfm_matcher *m, int view, int shard, osfm_view_bank *bank);
 OSFM_API int osfm_match_debug_set_view_device(osfm_matcher *m, int view, const float *sift, int n_sift, const int32_t *sift_order,
     const float *surf, int n_surf, const int32_t *surf_order, const float *positions);
+
+/* ---- Sub-pixel refinement of track observations by affine least-squares patch matching -------------------------
+ * No counterpart in the reference; a caller of it inserts the step behind calculateTracksUsingMVE.
+ * tests/refine_restatement.py is the definition, DESIGN.md "Observation refinement" describes it.  In short: the first
+ * alive observation of a track is its reference and never moves.  Its window T(u) = I_ref(p_ref + step u), u integer in
+ * [-radius, radius]^2, sampled bilinearly, is the template of every other alive observation t of the track, which is
+ * refined on its own: Gauss-Newton on T(u) ~ g I_t(p + A step u) + b over p (2), A (4), g and b, from the given
+ * position, init_affine (or the identity), g = 1, b = 0, until |dp| < eps.  Pixel centres are at integers, as in
+ * osfm_view_front_download's positions; a window is inside an image when every sample lies in [0, width - 1] x
+ * [0, height - 1].  A 3-channel pixel has the grey value (float)(r + g + b) / 3.0f.  Everything from the samples on is
+ * double arithmetic in a fixed order: a call repeats to the bit, and an observation's result does not depend on the
+ * other tracks.
+ *
+ * One status per observation; out_xy is the input position, to the bit, for every status but OSFM_REFINE_REFINED.  The
+ * first test that fails decides: */
+#define OSFM_REFINE_UNTESTED 0          /* dead, or fewer than two alive observations in its track */
+#define OSFM_REFINE_REFERENCE 1         /* the track's template */
+#define OSFM_REFINE_REFINED 2
+#define OSFM_REFINE_OUTSIDE 3           /* the template window, or the target window at any iteration or at the end, leaves its image */
+#define OSFM_REFINE_FLAT 4              /* standard deviation of the template below min_contrast */
+#define OSFM_REFINE_ILL_CONDITIONED 5   /* a pivot of the Cholesky factor of the diagonally scaled normal matrix below min_pivot */
+#define OSFM_REFINE_NOT_CONVERGED 6     /* max_iterations steps without |dp| < eps */
+#define OSFM_REFINE_REJECT_SHIFT 7      /* |p - p0| > max_shift */
+#define OSFM_REFINE_REJECT_DEFORM 8     /* a singular value of A A0^-1 outside [1 / max_deform, max_deform] */
+#define OSFM_REFINE_REJECT_SCORE 9      /* zero-mean normalised cross-correlation of the final patch and the template below min_score */
+#define OSFM_REFINE_NUM_STATUS 10
+
+typedef struct osfm_refine_options {
+    int32_t radius;           /* 7: a 15 x 15 window; 2..15 */
+    int32_t max_iterations;   /* 10; 1..100 */
+    double step;              /* 1.0: pixels between neighbouring samples of the template; > 0 */
+    double eps;               /* 1e-3 px */
+    double min_contrast;      /* 2.0 grey levels */
+    double max_shift;         /* 3.0 px */
+    double max_deform;        /* 2.0; >= 1 */
+    double min_score;         /* 0.9; -1..1 */
+    double min_pivot;         /* 0.034 (how it was measured: DESIGN.md); 0 < min_pivot < 1 */
+} osfm_refine_options;
+OSFM_API int osfm_refine_options_default(osfm_refine_options *opts);
+
+typedef struct osfm_refine_stats {
+    int64_t status_count[OSFM_REFINE_NUM_STATUS];   /* observations per status */
+    int64_t iterations;                             /* Gauss-Newton steps taken, summed */
+    double device_ms;                               /* the two kernels, by device events */
+} osfm_refine_stats;
+
+typedef struct osfm_refiner osfm_refiner;
+
+/* A refiner holds one grey image (float32, booked in osfm_library_memory as device_buffer_bytes) per view it was given. */
+OSFM_API int osfm_refine_create(int device, int num_views, osfm_refiner **out);
+OSFM_API int osfm_refine_destroy(osfm_refiner *r);
+/* The image of a view, 8-bit, row-major, 1 or 3 interleaved channels, from host memory; the grey conversion runs on
+ * the device.  OSFM_E_RANGE: view outside [0, num_views); OSFM_E_ARG: channels, a size outside 1..16384. */
+OSFM_API int osfm_refine_set_image(osfm_refiner *r, int view, const uint8_t *pixels, int width, int height, int channels);
+/* The same from the feature image of the front end's last load (what osfm_view_front_debug_image shows), device to
+ * device, ordered against the front end's next load as osfm_match_set_view_from_front is.  OSFM_E_STATE without a
+ * load; OSFM_E_ARG when the front end lives on another device. */
+OSFM_API int osfm_refine_set_image_from_front(osfm_refiner *r, int view, osfm_view_front *front);
+
+/* Tracks as CSR: observation f of track t for offsets[t] <= f < offsets[t + 1], F = offsets[num_tracks].  view [F],
+ * xy [F][2] (pixels of the view's image), alive [F] (NULL: all alive), init_affine [F][4] row-major (NULL: identity),
+ * opts NULL: the defaults.  Outputs, each [F] rows: out_xy [F][2], out_affine [F][4] (the refined A of REFINED
+ * observations, the initial one of every other), score [F] (where the final patch was compared, else 0), status [F],
+ * iterations [F]; out_affine, score, iterations and stats may be NULL.
+ *   OSFM_E_ARG    null arguments, offsets that do not start at 0 or decrease, options out of range, a non-finite
+ *                 position or init_affine, a singular init_affine
+ *   OSFM_E_RANGE  a view id outside [0, num_views)
+ *   OSFM_E_STATE  an alive observation in a view without an image
+ * None of them writes an output. */
+OSFM_API int osfm_refine_tracks(osfm_refiner *r, int64_t num_tracks, const int64_t *offsets, const int32_t *view, const double *xy,
+    const uint8_t *alive, const double *init_affine, const osfm_refine_options *opts, double *out_xy, double *out_affine,
+    double *score, int32_t *status, int32_t *iterations, osfm_refine_stats *stats);
 
 #ifdef __cplusplus
 }

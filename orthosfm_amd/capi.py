@@ -324,6 +324,28 @@ class ConsensusStats(C.Structure):
 CONSENSUS_UNTESTED, CONSENSUS_CLEAN, CONSENSUS_REPAIRED, CONSENSUS_UNSUPPORTED, CONSENSUS_DEGENERATE = 0, 1, 2, 3, 4
 CONSENSUS_MAX_REFIT_ROUNDS = 16
 
+class RefineOptions(C.Structure):
+    """osfm_refine_options."""
+    _fields_ = [("radius", C.c_int32), ("max_iterations", C.c_int32)] + \
+               [(n, C.c_double) for n in ("step", "eps", "min_contrast", "max_shift", "max_deform", "min_score", "min_pivot")]
+
+
+REFINE_STATUS = ("untested", "reference", "refined", "outside", "flat", "ill_conditioned", "not_converged", "reject_shift",
+                 "reject_deform", "reject_score")
+(REFINE_UNTESTED, REFINE_REFERENCE, REFINE_REFINED, REFINE_OUTSIDE, REFINE_FLAT, REFINE_ILL_CONDITIONED, REFINE_NOT_CONVERGED,
+ REFINE_REJECT_SHIFT, REFINE_REJECT_DEFORM, REFINE_REJECT_SCORE) = range(10)
+
+
+class RefineStats(C.Structure):
+    """osfm_refine_stats."""
+    _fields_ = [("status_count", C.c_int64 * len(REFINE_STATUS)), ("iterations", C.c_int64), ("device_ms", C.c_double)]
+
+    def counters(self) -> dict:
+        d = {n: int(self.status_count[i]) for i, n in enumerate(REFINE_STATUS)}
+        d["iterations"] = int(self.iterations)
+        return d
+
+
 # every symbol include/osfm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "osfm_last_error", "osfm_version", "osfm_device_count", "osfm_device_memory", "osfm_library_memory", "osfm_trim_device_memory", "osfm_ransac_selfcheck", "osfm_ba_debug_chol_trace", "osfm_ba_debug_flow_spin_limit", "osfm_ba_debug_order",
@@ -360,6 +382,8 @@ EXPORTS = [
     "osfm_match_debug_view_bank", "osfm_match_debug_set_view_device",
     "osfm_view_mark_options_default", "osfm_view_front_load_marked", "osfm_view_front_download_marks", "osfm_view_debug_mark_rows",
     "osfm_tracks_filter_marked",
+    "osfm_refine_options_default", "osfm_refine_create", "osfm_refine_destroy", "osfm_refine_set_image",
+    "osfm_refine_set_image_from_front", "osfm_refine_tracks",
 ]
 
 # osfm_track_feature as a numpy record (32 bytes, no padding)
@@ -431,6 +455,13 @@ lib.osfm_consensus_get_limits.restype = None
 lib.osfm_consensus_get_limits.argtypes = [C.POINTER(ConsensusLimits)]
 lib.osfm_ba_consensus.argtypes = [C.c_void_p, C.POINTER(ConsensusOptions)] + [C.c_void_p] * 5 + [C.POINTER(ConsensusStats)]
 lib.osfm_scene_filter_consensus.argtypes = [C.c_void_p, C.POINTER(ConsensusOptions), C.POINTER(ConsensusStats)]
+lib.osfm_refine_options_default.argtypes = [C.POINTER(RefineOptions)]
+lib.osfm_refine_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+lib.osfm_refine_destroy.argtypes = [C.c_void_p]
+lib.osfm_refine_set_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
+lib.osfm_refine_set_image_from_front.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+lib.osfm_refine_tracks.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(RefineOptions)] + [C.c_void_p] * 5 + \
+                                  [C.POINTER(RefineStats)]
 lib.osfm_ba_debug_cholesky_solve.restype = C.c_int
 lib.osfm_ba_debug_cholesky_solve.argtypes = [C.c_int, C.c_int, _f64p, _f64p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, _f64p, _i32p, _i32p]
@@ -543,6 +574,17 @@ def consensus_limits() -> ConsensusLimits:
     l = ConsensusLimits()
     lib.osfm_consensus_get_limits(C.byref(l))
     return l
+
+
+def default_refine_options(**kw) -> RefineOptions:
+    """osfm_refine_options_default with the given fields replaced."""
+    o = RefineOptions()
+    check(lib.osfm_refine_options_default(C.byref(o)))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"osfm_refine_options has no field {k!r}")
+        setattr(o, k, v)
+    return o
 
 
 def default_sift_options() -> SiftOptions:

@@ -273,6 +273,15 @@ int view_front_result(osfm_view_front *c, FrontResult *out)
     return OSFM_OK;
 }
 
+int view_front_image(osfm_view_front *c, FrontImage *out)
+{
+    if (!c || !out) { set_error("osfm_view_front: null argument"); return OSFM_E_ARG; }
+    if (!c->have) { set_error("osfm_view_front: no load whose image could be handed off"); return OSFM_E_STATE; }
+    out->device = c->device; out->pixels = c->d_image;
+    out->width = c->feat_w; out->height = c->feat_h; out->channels = c->channels;
+    return OSFM_OK;
+}
+
 int view_front_begin_read(osfm_view_front *c, hipStream_t reader)
 {
     OSFM_HIP_CHECK(hipStreamWaitEvent(reader, c->ev[3], 0));

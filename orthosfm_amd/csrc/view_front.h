@@ -23,4 +23,13 @@ int view_front_result(osfm_view_front *front, FrontResult *out);
 int view_front_begin_read(osfm_view_front *front, hipStream_t reader);
 int view_front_end_read(osfm_view_front *front, hipStream_t reader);
 
+// The feature image of the last load (what osfm_view_front_debug_image copies out), for a reader inside the same
+// brackets: 8-bit, row-major, `channels` interleaved.  OSFM_E_STATE without a load.
+struct FrontImage {
+    int device = 0;
+    const uint8_t *pixels = nullptr;
+    int width = 0, height = 0, channels = 0;
+};
+int view_front_image(osfm_view_front *front, FrontImage *out);
+
 }  // namespace osfm

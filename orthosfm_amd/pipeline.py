@@ -350,6 +350,7 @@ class Timings:
     global_ba_s: float = 0.0
     outlier_filter_s: float = 0.0
     consensus_filter_s: float = 0.0   # track_filter="consensus": the per-track consensus filter behind the global adjustments
+    refine_s: float = 0.0         # tracks_from_images(refine=True): the sub-pixel refinement of the finished table
     pose_host_s: float = 0.0
     pose_s: float = 0.0
     total_s: float = 0.0
@@ -463,7 +464,7 @@ def match_and_build_tracks(iset, matcher="exhaustive", device=0, verify=True, ti
 
 def tracks_from_images(images, matcher="exhaustive", device=0, verify=True, downscale_factor=1, max_image_size=6_000_000,
                        options=None, timings=None, pairs=None, masks=None, mask_mode="tracks", mask_clamp="reference",
-                       feature_colors=False, guided=False):
+                       feature_colors=False, guided=False, refine=False):
     """calculateTracksUsingMVE from decoded images onwards: every image (uint8 [h, w] or [h, w, 3]) goes through a
     features.ViewFrontEnd -- the halving chain, SIFT and SURF, colours and normalised positions on the device -- and
     from there into the matcher without the descriptors' way through the host; then matching, RANSAC-F, the tracks
@@ -479,7 +480,13 @@ def tracks_from_images(images, matcher="exhaustive", device=0, verify=True, down
     of View::isPixelMaskedIn as written) or "image".  feature_colors: info["feature_rgb"] holds
     propagateColorsToTracks' colour per track feature, in the table's feature order, for save_project.  Either needs
     one import width for all views, else ValueError: the reference's imageWidth there is whichever thread wrote last.
-    info["mask"] carries the counts."""
+    info["mask"] carries the counts.
+
+    refine: True (or a dict of osfm_refine_options fields) sends the finished table through refine.Refiner: every
+    view's feature image is handed over on the device inside its upload, every observation but the first of its track
+    is refined against that first one from the detectors' scale and orientation, and the REFINED ones take the new
+    position, rounded to float32 as Feature::x/y hold it.  info["refine"] has the counts and the status per
+    observation, Timings.refine_s the time.  This step has no counterpart in the reference; False changes nothing."""
     from .features import ViewFrontEnd, _mark_options
     images = [np.asarray(im) for im in images]
     if not images:
@@ -502,6 +509,10 @@ def tracks_from_images(images, matcher="exhaustive", device=0, verify=True, down
                          max_image_size)
     colors, width = [None] * V, [0]
     norms, marks, pixel_rgb, counts = [None] * V, [None] * V, [None] * V, [None] * V
+    refiner, shapes = None, [None] * V          # refine: per view (feature width, feature height, scale, orientation)
+    if refine:
+        from .refine import Refiner
+        refiner = Refiner(device, V)
 
     def upload(m, v):
         if marked:
@@ -510,6 +521,10 @@ def tracks_from_images(images, matcher="exhaustive", device=0, verify=True, down
             s = front.load(images[v])
         m.set_view_from_front(v, front)
         fs = front.download()
+        if refiner is not None:
+            refiner.set_image_from_front(v, front)
+            shapes[v] = (fs.feature_width, fs.feature_height, np.concatenate([fs.sift.scale, fs.surf.scale]),
+                         np.concatenate([fs.sift.orientation, fs.surf.orientation]))
         colors[v], width[0] = fs.colors, s.import_width
         if marked:
             _, pixel_rgb[v], marks[v] = front.download_marks()
@@ -519,10 +534,47 @@ def tracks_from_images(images, matcher="exhaustive", device=0, verify=True, down
     try:
         tt, info, tcol = _match_and_build(V, upload, None, lambda: width[0], matcher, device, verify, timings, pairs,
                                           options, colors, guided=guided)
+        if marked:
+            tt, tcol = _apply_marks(tt, tcol, info, V, masks, mask_mode, mask_clamp, marks, norms, pixel_rgb, counts, width[0],
+                                    feature_colors)
+        if refiner is not None:
+            t0 = time.perf_counter()
+            info["refine"] = _refine_table(tt, refiner, shapes, width[0], refine if isinstance(refine, dict) else {})
+            if timings is not None:
+                timings.refine_s = time.perf_counter() - t0
     finally:
         front.close()
-    if not marked:
-        return tt, tcol, info
+        if refiner is not None:
+            refiner.close()
+    return tt, tcol, info
+
+
+def _refine_table(tt, refiner, shapes, import_width, options):
+    """tracks_from_images(refine=True): the table's positions into pixels of each view's feature image (the inverse of
+    TrackTable.from_mve's expression: import_width * (n + 0.5) on both axes with n normalised by max(w, h) of the
+    feature image), through Refiner.refine, and the REFINED ones back, rounded to float32."""
+    from .refine import relative_affine
+    fw = np.array([s[0] for s in shapes], dtype=np.float64)[tt.view]
+    fh = np.array([s[1] for s in shapes], dtype=np.float64)[tt.view]
+    side = np.maximum(fw, fh)
+    half = np.stack([fw, fh], axis=1) / 2.0
+    starts = np.concatenate([[0], np.cumsum([s[2].shape[0] for s in shapes])]).astype(np.int64)
+    row = starts[tt.view] + tt.feat
+    scale, theta = np.concatenate([s[2] for s in shapes])[row], np.concatenate([s[3] for s in shapes])[row]
+    xy = (tt.xy / float(import_width) - 0.5) * side[:, None] + half - 0.5
+    res = refiner.refine(tt.offsets, tt.view, xy, init_affine=relative_affine(tt.offsets, scale, theta), **options)
+    sel = res.refined
+    back = float(import_width) * ((res.xy[sel] + 0.5 - half[sel]) / side[sel, None] + 0.5)
+    tt.xy[sel] = back.astype(np.float32).astype(np.float64)
+    out = res.stats.counters()
+    out["device_ms"] = float(res.stats.device_ms)
+    out["status"] = res.status
+    return out
+
+
+def _apply_marks(tt, tcol, info, V, masks, mask_mode, mask_clamp, marks, norms, pixel_rgb, counts, width, feature_colors):
+    """tracks_from_images with masks or feature colours: filterTracksWithMasks on the finished table, info["mask"] and
+    info["feature_rgb"]."""
     has_mask = [masks is not None and masks[v] is not None for v in range(V)]
     mask_info = {"mode": mask_mode, "clamp": mask_clamp, "tracks_built": int(tt.offsets.shape[0] - 1), "tracks_dropped": 0}
     for k in ("masked_out_sift", "masked_out_surf", "outside", "kept_sift", "kept_surf"):
@@ -532,14 +584,14 @@ def tracks_from_images(images, matcher="exhaustive", device=0, verify=True, down
         if not keep.all():
             kept_f = keep[tt.track_of]
             offsets = np.concatenate([[0], np.cumsum(np.diff(tt.offsets)[keep])]).astype(np.int64)
-            tt = TrackTable.from_mve(offsets, np.stack([tt.view[kept_f], tt.feat[kept_f]], axis=1), norms, width[0], V)
+            tt = TrackTable.from_mve(offsets, np.stack([tt.view[kept_f], tt.feat[kept_f]], axis=1), norms, width, V)
             tcol = tcol[keep]
             mask_info["tracks_dropped"] = int((~keep).sum())
     info["mask"] = mask_info
     if feature_colors:
         starts = np.concatenate([[0], np.cumsum([len(p) for p in pixel_rgb])]).astype(np.int64)
         info["feature_rgb"] = np.concatenate(pixel_rgb)[starts[tt.view] + tt.feat]
-    return tt, tcol, info
+    return tt, tcol
 
 
 def _match_and_build(V, upload, sizes, image_width, matcher, device, verify, timings, pairs, options, colors, guided=False):
