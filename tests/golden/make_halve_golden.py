@@ -1,5 +1,6 @@
 """Writes tests/golden/halve_reference.npz: what the reference's mve::image::rescale_half_size<uint8_t> makes of every
-image of tests/view_cases.halve_images(), as bytes in the output's shape, and under "refused" whether it threw on
+image of tests/view_cases.halve_images(), as bytes in the output's shape, every step of the chains of
+view_cases.HALVE_CHAINS (the reference halving its own last result), and under "refused" whether it threw on
 view_cases.REFUSED_SHAPE.
 
 The reference is compiled here from its own headers (REF, as in make_sift_golden.py) with the driver beside this file
@@ -53,6 +54,11 @@ def main():
         for name, img in vc.halve_images().items():
             out[name] = run_reference(exe, tmp, name, img)
             assert out[name] is not None, name
+        for (w, h, n), img in vc.chain_images().items():
+            for step in range(1, n + 1):
+                img = run_reference(exe, tmp, vc.chain_name(w, h, step), img)
+                assert img is not None, (w, h, step)
+                out[vc.chain_name(w, h, step)] = img
         w, h, c = vc.REFUSED_SHAPE
         out["refused"] = np.array(run_reference(exe, tmp, "refused", np.zeros((h, w), np.uint8)) is None)
     # an .npz whose bytes depend on its arrays alone: fixed entry order and time stamps
@@ -68,6 +74,10 @@ def main():
     vc.golden.cache_clear()
     for name, img in vc.halve_images().items():
         assert vc.halve(img).tobytes() == vc.golden()[name].tobytes() and vc.halve(img).shape == vc.golden()[name].shape, name
+    for (w, h, n), img in vc.chain_images().items():
+        for step in range(1, n + 1):
+            img = vc.halve(img)
+            assert img.tobytes() == vc.golden()[vc.chain_name(w, h, step)].tobytes(), (w, h, step)
     print(len(out) - 1, "images: the restatement equals the reference")
 
 

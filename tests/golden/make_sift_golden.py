@@ -1,7 +1,9 @@
 """Writes tests/golden/sift_reference.npz: per case of tests/sift_cases.py what the reference SIFT detector makes of
 the case's image, stage by stage -- the SHA-256 of the input, of every octave image and of every DoG image, the
 candidate list, the localised keypoints, the descriptors with x, y, scale and orientation in generation order, and
-the FeatureSet view (the permutation that sorts by scale, colours, normalised positions).
+the FeatureSet view (the permutation that sorts by scale, colours, normalised positions).  For the cases of
+sift_cases.EDGE it keeps the hashes, the candidates, the keypoints and whether the reference threw, and checks that
+every octave of at least sift_cases.MIN_SIDE pixels a side holds a candidate.
 
 The reference is compiled here from its own sources (REF, default /root/reference) with the driver beside this file
 into a temporary directory; nothing of it enters the tree.  The script then holds the numpy restatement
@@ -60,7 +62,10 @@ def run_reference(exe, tmp, case):
     raw = os.path.join(tmp, case.name + ".raw")
     img.tofile(raw)
     out = os.path.join(tmp, case.name + ".bin")
-    subprocess.check_call([exe, raw, str(case.width), str(case.height), str(case.channels), str(case.min_octave), out])
+    args = [exe, raw, str(case.width), str(case.height), str(case.channels), str(case.min_octave), out]
+    if (case.samples, case.base_blur_sigma) != (3, 1.6):
+        args += [str(case.samples), repr(case.base_blur_sigma)]
+    subprocess.check_call(args)
     return read_records(out)
 
 
@@ -70,11 +75,14 @@ def fixture_of(case, rec):
     if fx["threw"]:
         return fx
     n_oct = len({k.split("/")[1] for k in rec if k.startswith("img/")})
-    fx["img_sha"] = np.array([[sc.sha(rec[f"img/{o}/{i}"]) for i in range(6)] for o in range(n_oct)], dtype="S64")
-    fx["dog_sha"] = np.array([[sc.sha(rec[f"dog/{o}/{i}"]) for i in range(5)] for o in range(n_oct)], dtype="S64")
+    S = case.samples
+    fx["img_sha"] = np.array([[sc.sha(rec[f"img/{o}/{i}"]) for i in range(S + 3)] for o in range(n_oct)], dtype="S64")
+    fx["dog_sha"] = np.array([[sc.sha(rec[f"dog/{o}/{i}"]) for i in range(S + 2)] for o in range(n_oct)], dtype="S64")
     fx["octave_shape"] = np.array([rec[f"img/{o}/0"].shape for o in range(n_oct)], dtype=np.int32)
     fx["candidates"] = rec["candidates"].astype(np.float32).reshape(-1, 4)
     fx["keypoints"] = rec["keypoints"].astype(np.float32).reshape(-1, 4)
+    if case.name in sc.EDGE:            # stage hashes, candidates, keypoints and the refused flag alone
+        return fx
     fx["gen_meta"] = rec["gen/meta"].reshape(-1, 4)
     fx["gen_data"] = rec["gen/data"].reshape(-1, 128)
     # the sorted view as a permutation of the generation order (rows are told apart by their bytes)
@@ -91,7 +99,7 @@ def fixture_of(case, rec):
 
 def check_case(case, fx):
     """Holds the restatement against the fixture and returns the measured figures of the case."""
-    opts = sr.Options(min_octave=case.min_octave)
+    opts = sc.options(case)
     assert bool(fx["threw"]) == case.refused == sr.refuses(case.width, case.height, opts), case.name
     if case.refused:
         print(f"{case.name:8s} the reference throws")
@@ -105,10 +113,15 @@ def check_case(case, fx):
     assert kps.tobytes() == fx["keypoints"].tobytes(), f"{case.name}: keypoints differ"
     per_oct = {int(o): int((kps[:, 0] == o).sum()) for o in np.unique(kps[:, 0])}
     fired = rejected.sum(0)
-    print(f"{case.name:8s} candidates {len(cand)} keypoints {len(kps)} per octave {per_oct} descriptors {len(fx['gen_meta'])} "
+    n_desc = len(fx["gen_meta"]) if "gen_meta" in fx else "not kept"
+    print(f"{case.name:8s} candidates {len(cand)} keypoints {len(kps)} per octave {per_oct} descriptors {n_desc} "
           f"moved {int(moved.sum())} singular {int(singular.sum())}")
     print(f"{'':8s} rejections " + ", ".join(f"{n} {int(c)}" for n, c in zip(sr.REJECTION_TESTS, fired))
           + "; never fired: " + (", ".join(n for n, c in zip(sr.REJECTION_TESTS, fired) if not c) or "none"))
+    if case.name in sc.EDGE:
+        sides = {o[0]: min(o[1][0].shape) for o in octs}
+        assert all((cand[:, 0] == o).any() for o, side in sides.items() if side >= sc.MIN_SIDE), f"{case.name}: an octave without candidates"
+        return None
     if not case.descriptors:
         assert len(fx["gen_meta"]) == 0, f"{case.name} has descriptors: hold it to the descriptor checks"
         return None

@@ -108,6 +108,8 @@ def check_case(case):
     print(f"{'':8s} ambiguous {n_amb} of {n_ori} keypoints with an orientation ({share:.2f} %), guarded "
           f"{sum(r['status'] == 2 for r in rows)}")
     assert n_amb <= 0.02 * max(1, n_ori), f"{case.name}: too many ambiguous keypoints, pick another seed"
+    if case.name in uc.EDGE:
+        assert all((cand[:, 0] == o).any() for o in uc.capable_octaves(case.width, case.height)), f"{case.name}: an octave without candidates"
     if case.counts:
         got = (len(cand), len(kps), len(fx["gen_meta"]))
         assert all(w is None or w == g for w, g in zip(case.counts, got)), (case.name, got)

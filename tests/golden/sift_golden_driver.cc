@@ -3,8 +3,10 @@
 // reference's sfm/sift.cc and mve/image_tools.cc with -fno-access-control (the stages are private members);
 // this file holds no reference code, only calls into it.
 //
-//   sift_golden_driver IMAGE.raw WIDTH HEIGHT CHANNELS MIN_OCTAVE OUT.bin      stage dump
-//   sift_golden_driver IMAGE.raw WIDTH HEIGHT CHANNELS MIN_OCTAVE --time N     Sift::process, milliseconds per run
+//   sift_golden_driver IMAGE.raw WIDTH HEIGHT CHANNELS MIN_OCTAVE OUT.bin [SAMPLES SIGMA]   stage dump
+//   sift_golden_driver IMAGE.raw WIDTH HEIGHT CHANNELS MIN_OCTAVE --time N                  Sift::process, milliseconds per run
+//
+// SAMPLES, SIGMA: num_samples_per_octave and base_blur_sigma where a case sets them; the defaults otherwise.
 //
 // Record: u32 name length, name, u8 type ('f' float32, 'i' int32, 'b' uint8), u32 rows, u32 cols, data.
 #include <algorithm>
@@ -51,7 +53,7 @@ static bool by_scale(const sfm::Sift::Descriptor &a, const sfm::Sift::Descriptor
 
 int main(int argc, char **argv)
 {
-    if (argc != 7 && argc != 8) { fprintf(stderr, "usage: see the head of the source\n"); return 2; }
+    if (argc != 7 && argc != 8 && argc != 9) { fprintf(stderr, "usage: see the head of the source\n"); return 2; }
     const int w = atoi(argv[2]), h = atoi(argv[3]), c = atoi(argv[4]);
     mve::ByteImage::Ptr img = mve::ByteImage::create(w, h, c);
     FILE *in = fopen(argv[1], "rb");
@@ -62,6 +64,10 @@ int main(int argc, char **argv)
     fclose(in);
     sfm::Sift::Options opts;
     opts.min_octave = atoi(argv[5]);
+    if (argc == 9) {
+        opts.num_samples_per_octave = atoi(argv[7]);
+        opts.base_blur_sigma = strtof(argv[8], nullptr);
+    }
 
     if (!strcmp(argv[6], "--time")) {
         const int runs = atoi(argv[7]);

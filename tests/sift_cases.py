@@ -3,7 +3,9 @@
 An image is a sum of anisotropic Gaussian blobs of either sign on a mid-grey ground, with log-uniform sizes
 and uniform angles, drawn from the repository's splitmix streams (orthosfm_amd.synth.uniform) and rendered to
 8 bits.  A 3-channel case gives every blob its own colour.  A crop case cuts a window out of a larger canvas,
-so that two crops that differ by an integer shift show the same structures.
+so that two crops that differ by an integer shift show the same structures.  EDGE_CASES are small images whose
+octaves stand on the constants of the kernels (segments of 256 pixels, tiles of 32, a radius of 32, the 2-pixel bound of
+the last octave), and the sweep cuts every accepted width and height up to 80 out of one image.
 
 tests/golden/make_sift_golden.py runs the reference detector on every case and writes
 tests/golden/sift_reference.npz; tests/sift_restatement.py restates the detector in numpy;
@@ -38,6 +40,8 @@ class Case:
     refused: bool = False         # the reference throws on this size
     descriptors: bool = True      # held to the orientation / descriptor checks
     faint: float = 0.0            # share of the blobs drawn at a twelfth of the amplitude: candidates that fail the contrast test
+    samples: int = 3              # Sift::Options::num_samples_per_octave
+    base_blur_sigma: float = 1.6  # Sift::Options::base_blur_sigma
 
 
 CASES = [
@@ -51,6 +55,41 @@ CASES = [
     Case("crop_a", 160, 120, 1, 300, 5, crop=(260, 190, 10, 12)),
     Case("crop_b", 160, 120, 1, 300, 5, crop=(260, 190, 37, 29)),
 ]
+
+# ---- image-shape edges of sift_kernels.hip and sift_api.hip; tests/test_sift_cases_cpu.py asserts what each one is
+# there for.  Seeds are picked so that every octave of at least MIN_SIDE pixels a side holds a candidate.
+_E = dict(descriptors=False)
+EDGE_CASES = [
+    # blur_rows_kernel stages 256 pixels and a halo: two exact segments and one (octaves 0 and 1), one exact segment
+    Case("w512", 512, 35, 1, 6, 70, sigma_hi=6.0, **_E),
+    Case("w256", 256, 35, 1, 6, 27, sigma_hi=6.0, **_E),
+    # a second segment of 33 pixels, and one of 3, narrower than every blur radius of the defaults (4 to 9)
+    Case("w289", 289, 33, 1, 12, 25, sigma_hi=6.0, **_E),
+    Case("w259", 259, 33, 1, 6, 25, sigma_hi=6.0, **_E),
+    # blur_cols_kernel works on 32 x 32 tiles: octaves of 64 x 65, 32 x 33 and 33 x 32
+    Case("c64x65", 64, 65, 1, 48, 109, **_E),
+    Case("c33x32", 33, 32, 1, 24, 31, **_E),
+    # octave_sizes(): the smallest accepted side is 17 (the fifth octave is 2 pixels), 16 is refused
+    Case("min40x17", 40, 17, 1, 6, 23, sigma_hi=6.0, **_E),
+    Case("min17x40", 17, 40, 1, 6, 23, sigma_hi=6.0, **_E),
+    Case("ref40x16", 40, 16, 1, 3, 5, sigma_hi=3.0, refused=True, **_E),
+    Case("ref16x40", 16, 40, 1, 3, 5, sigma_hi=3.0, refused=True, **_E),
+    # the largest side whose last octave is 2 pixels: extrema_blocks() == 0 there and nothing is launched
+    Case("two40x32", 40, 32, 1, 24, 31, **_E),
+    Case("two32x40", 32, 40, 1, 48, 46, **_E),
+    Case("up17x19", 17, 19, 1, 6, 105, min_octave=-1, sigma_hi=6.0, **_E),
+    # extrema_kernel numbers interior pixels in blocks of 256: 16 x 16 = 256 and 17 x 16 = 272 of them in octave 0
+    Case("int18x18", 18, 18, 1, 6, 105, sigma_hi=6.0, **_E),
+    Case("int19x18", 19, 18, 1, 24, 31, sigma_hi=6.0, **_E),
+    # one sample per octave at the default base blur: the last blur step has sigma 1.6 sqrt(48) = 11.085 and a radius of
+    # ceil(11.085 * 2.884) = 32 = kMaxRadius, which fills both LDS tiles; in the 80 x 70 of octave 0 columns 32 to 47 and rows
+    # 32 to 37 read 32 pixels either way unclamped, every other pixel and every later octave reads clamped ones
+    Case("r32", 80, 70, 1, 6, 161, sigma_hi=6.0, samples=1, **_E),
+]
+EDGE = [c.name for c in EDGE_CASES]
+CASES += EDGE_CASES
+MIN_SIDE = 8                      # below it no seed gave a candidate: every blur radius exceeds the octave, which is all border
+RADIUS_REFUSED_SIGMA = 1.61       # with one sample per octave: a radius of 33
 BY_NAME = {c.name: c for c in CASES}
 SHIFT = (27, 17)                  # crop_b's origin minus crop_a's: a point at x in crop_a lies at x - SHIFT in crop_b
 
@@ -113,6 +152,14 @@ def image(name):
     return img
 
 
+def options(case):
+    """The Sift::Options of a case, as the restatement takes them; a negative contrast threshold means 0.02 / samples."""
+    import sift_restatement as sr
+    f32 = np.float32
+    return sr.Options(min_octave=case.min_octave, num_samples_per_octave=case.samples,
+                      contrast_threshold=f32(0.02) / f32(case.samples), base_blur_sigma=f32(case.base_blur_sigma))
+
+
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
@@ -155,13 +202,53 @@ def restated(name):
     """(octaves, candidates, keypoints, float64 describe(), float32 describe()) of the restatement.  Cached."""
     import sift_restatement as sr
     c = BY_NAME[name]
-    opts = sr.Options(min_octave=c.min_octave)
+    opts = options(c)
     octs = sr.scale_space(image(name), opts)
     cand = sr.extrema(octs)
     kps = sr.localise(octs, cand, opts)[0]
     d64 = sr.describe(octs, kps, opts, np.float64) if c.descriptors else None
     d32 = sr.describe(octs, kps, opts, np.float32) if c.descriptors else None
     return octs, cand, kps, d64, d32
+
+
+# ---- the sweep: every accepted width at the full height and every accepted height at the full width, all cut from the
+# top-left corner of one image, so that every clamp and every segment and tile bound is crossed one pixel at a time
+SWEEP_SIDE = 80
+SWEEP_SMALLEST = 17               # octave_sizes() refuses 16
+SWEEP_SHAPES = ([(w, SWEEP_SIDE) for w in range(SWEEP_SMALLEST, SWEEP_SIDE + 1)]
+                + [(SWEEP_SIDE, h) for h in range(SWEEP_SMALLEST, SWEEP_SIDE)])          # (w, h)
+SWEEP_CHUNK = 16
+SWEEP_CHUNKS = [SWEEP_SHAPES[i:i + SWEEP_CHUNK] for i in range(0, len(SWEEP_SHAPES), SWEEP_CHUNK)]
+
+
+@lru_cache(maxsize=None)
+def sweep_image():
+    img = render(SWEEP_SIDE, SWEEP_SIDE, 1, 40, 9, 1.0, 8.0)
+    img.setflags(write=False)
+    return img
+
+
+def sweep_cut(w, h, source=None):
+    return np.ascontiguousarray((sweep_image() if source is None else source)[:h, :w])
+
+
+def stage_hashes(images, dogs, cand, kps):
+    """[(stage, SHA-256)] of one extraction: images[o][i] and dogs[o][i] per octave, candidates, keypoints."""
+    out = []
+    for o, (im, dg) in enumerate(zip(images, dogs)):
+        out += [(f"octave {o} image {i}", sha(a)) for i, a in enumerate(im)]
+        out += [(f"octave {o} DoG {i}", sha(a)) for i, a in enumerate(dg)]
+    return out + [("candidates", sha(cand)), ("keypoints", sha(kps))]
+
+
+@lru_cache(maxsize=None)
+def sweep_restated(w, h):
+    """stage_hashes of the restatement on the sweep's w x h cut.  Cached."""
+    import sift_restatement as sr
+    opts = sr.Options()
+    octs = sr.scale_space(sweep_cut(w, h), opts)
+    cand = sr.extrema(octs)
+    return stage_hashes([o[1] for o in octs], [o[2] for o in octs], cand, sr.localise(octs, cand, opts)[0])
 
 
 def measure(name):

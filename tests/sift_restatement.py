@@ -66,11 +66,26 @@ def gaussian_weights(sigma):
     return ks, np.array(w, dtype=f32)
 
 
-def _border(idx, n, unclamped):
+def _border(idx, n, unclamped, mirrored=False):
+    if mirrored:                    # ... 1 0 | 0 1 ... n-1 | n-1 n-2 ...
+        m = idx % (2 * n)
+        return np.where(m < n, m, 2 * n - 1 - m)
     return idx % n if unclamped else np.clip(idx, 0, n - 1)
 
 
-def blur_gaussian(img, sigma, plant_reversed_taps=False, plant_unclamped=False):
+def blur_radii(opts):
+    """The blur radius of every image of an octave after the first: (ks of image 1, ..., ks of image S + 2)."""
+    S = opts.num_samples_per_octave
+    k = powf(2.0, f32(1.0) / f32(S))
+    sigma, out = opts.base_blur_sigma, []
+    for _ in range(1, S + 3):
+        sigmak = sigma * k
+        out.append(gaussian_weights(np.sqrt(sigmak * sigmak - sigma * sigma, dtype=f32))[0])
+        sigma = sigmak
+    return out
+
+
+def blur_gaussian(img, sigma, plant_reversed_taps=False, plant_unclamped=False, plant_mirrored=False):
     ks, wt = gaussian_weights(sigma)
     if wt is None:
         return img.copy()
@@ -82,7 +97,7 @@ def blur_gaussian(img, sigma, plant_reversed_taps=False, plant_unclamped=False):
         wsum = f32(0.0)
         base = np.arange(n)
         for i in taps:
-            idx = _border(base + i, n, plant_unclamped)
+            idx = _border(base + i, n, plant_unclamped, plant_mirrored)
             acc = acc + np.take(out, idx, axis=axis) * wt[abs(i)]
             wsum = wsum + wt[abs(i)]
         out = acc / wsum

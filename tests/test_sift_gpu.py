@@ -5,7 +5,10 @@ Scale space, candidates and localised keypoints must be equal to the reference's
 descriptors are held to four times the measured distance between the reference and the float64 restatement
 (sift_cases.MEASURED): two independent float32 sums, each as far from the exact value as the reference's own, times
 two for the order of the reduction tree.  Keypoints with a peak decision inside the ambiguity band may differ in
-their number of orientations and are only counted."""
+their number of orientations and are only counted.
+
+The cases of sift_cases.EDGE_CASES go through the same parametrised tests; a sweep of every accepted width and height
+up to 80 on one context is held to the restatement stage by stage."""
 import ctypes as C
 
 import numpy as np
@@ -18,13 +21,15 @@ pytestmark = pytest.mark.gpu
 
 LIVE = [c.name for c in sc.CASES if not c.refused]
 DESCRIBED = ["base", "up", "rgb", "many"]
-MAX_W, MAX_H = 420, 320
+MAX_W, MAX_H = 520, 320
 
 
 @pytest.fixture(scope="module")
 def extractors():
     from orthosfm_amd.features import SiftExtractor
     ex = {0: SiftExtractor(0, MAX_W, MAX_H), -1: SiftExtractor(0, MAX_W, MAX_H, min_octave=-1)}
+    r32 = sc.BY_NAME["r32"]           # one sample per octave: a blur radius of kMaxRadius = 32
+    ex["r32"] = SiftExtractor(0, r32.width, r32.height, num_samples_per_octave=r32.samples, base_blur_sigma=r32.base_blur_sigma)
     yield ex
     for e in ex.values():
         e.close()
@@ -37,13 +42,13 @@ def extracted(extractors):
     out = {}
     for name in LIVE:
         c = sc.BY_NAME[name]
-        ex = extractors[c.min_octave]
+        ex = extractors["r32" if name == "r32" else c.min_octave]
         s = ex.run(sc.image(name))
         n_oct = s.num_octaves
         out[name] = dict(
             summary=(s.num_candidates, s.num_keypoints, s.num_descriptors, n_oct, list(s.keypoints_per_octave)[:n_oct]),
-            img=[[ex.debug_image(c.min_octave + o, 0, i) for i in range(6)] for o in range(n_oct)],
-            dog=[[ex.debug_image(c.min_octave + o, 1, i) for i in range(5)] for o in range(n_oct)],
+            img=[[ex.debug_image(c.min_octave + o, 0, i) for i in range(c.samples + 3)] for o in range(n_oct)],
+            dog=[[ex.debug_image(c.min_octave + o, 1, i) for i in range(c.samples + 2)] for o in range(n_oct)],
             cand=ex.debug_keypoints(False), kps=ex.debug_keypoints(True), features=ex.download())
     return out
 
@@ -76,6 +81,68 @@ def test_candidates_and_keypoints_equal_the_reference(name, extracted):
     assert n_desc == len(got["features"])
     mo = sc.BY_NAME[name].min_octave
     assert per_octave == [int((fx["keypoints"][:, 0] == mo + o).sum()) for o in range(n_oct)]
+
+
+def test_the_largest_blur_radius(extracted):
+    """`r32`: one sample per octave at the default base blur needs a radius of 32, which fills both LDS tiles of the
+    blur kernels to their last element; the scale space equals the restatement's (the parametrised tests above hold it
+    to the fixture).  One hundredth more sigma needs 33 and is refused."""
+    from orthosfm_amd import capi
+    from orthosfm_amd.features import SiftExtractor
+    c = sc.BY_NAME["r32"]
+    assert sr.blur_radii(sc.options(c)) == [8, 16, 32]
+    octs, cand, kps = sc.restated("r32")[:3]
+    got = extracted["r32"]
+    assert sc.stage_hashes(got["img"], got["dog"], got["cand"], got["kps"]) == \
+        sc.stage_hashes([o[1] for o in octs], [o[2] for o in octs], cand, kps)
+    assert len(got["img"]) == 5 and len(got["img"][0]) == 4 and len(got["cand"]) > 0
+    with pytest.raises(capi.OsfmError, match="blur radius of 33, the kernels hold 32") as e:
+        SiftExtractor(0, c.width, c.height, num_samples_per_octave=1, base_blur_sigma=sc.RADIUS_REFUSED_SIGMA)
+    assert e.value.status == capi.E_ARG
+
+
+@pytest.fixture(scope="module")
+def sweep_context():
+    """One context of 80 x 80 for the whole sweep, and what it made of the 80 x 80 window of `base` before any of it."""
+    from orthosfm_amd.features import SiftExtractor
+    with SiftExtractor(0, sc.SWEEP_SIDE, sc.SWEEP_SIDE) as ex:
+        yield ex, _all_bytes(ex, sc.sweep_cut(sc.SWEEP_SIDE, sc.SWEEP_SIDE, sc.image("base")))
+
+
+def _device_stage_hashes(ex):
+    n_oct = 5
+    return sc.stage_hashes([[ex.debug_image(o, 0, i) for i in range(6)] for o in range(n_oct)],
+                           [[ex.debug_image(o, 1, i) for i in range(5)] for o in range(n_oct)],
+                           ex.debug_keypoints(False), ex.debug_keypoints(True))
+
+
+@pytest.mark.parametrize("chunk", range(len(sc.SWEEP_CHUNKS)))
+def test_sweep_equals_the_restatement(chunk, sweep_context):
+    """Every width from 17 to 80 at height 80 and every height from 17 to 80 at width 80, cut from one image, on one
+    context: every scale-space and DoG image, the candidates and the keypoints against the restatement, hashed once a
+    side.  The restatement takes 1.3 s for all 127 shapes (one CPU core), so the range is not cut."""
+    ex = sweep_context[0]
+    for w, h in sc.SWEEP_CHUNKS[chunk]:
+        assert ex.run(sc.sweep_cut(w, h)).num_octaves == 5
+        got, want = _device_stage_hashes(ex), sc.sweep_restated(w, h)
+        assert len(got) == len(want)
+        differ = [f"{w} x {h}: {stage}" for (stage, a), (_, b) in zip(got, want) if a != b]
+        assert not differ, differ[:6]
+
+
+def test_sweep_leaves_nothing_behind(sweep_context):
+    """After shapes of every size on the context, the 80 x 80 window of `base` (`base` itself does not fit a context of
+    80 x 80) gives its earlier bytes, which are the restatement's: nothing depends on the image that was there before."""
+    ex, before = sweep_context
+    window = sc.sweep_cut(sc.SWEEP_SIDE, sc.SWEEP_SIDE, sc.image("base"))
+    for w, h in ((17, 80), (80, 17), (80, 80), (33, 80)):
+        ex.run(sc.sweep_cut(w, h))
+        assert _all_bytes(ex, window) == before
+    octs = sr.scale_space(window, sr.Options())
+    cand = sr.extrema(octs)
+    assert _device_stage_hashes(ex) == sc.stage_hashes([o[1] for o in octs], [o[2] for o in octs], cand,
+                                                       sr.localise(octs, cand, sr.Options())[0])
+    assert len(cand) > 0
 
 
 def test_options_reach_the_kernels():
@@ -208,6 +275,10 @@ def test_error_paths(extractors):
         assert (guard == 7.0).all()
 
     refused(ex, sc.image("refused"), 9, 9, 1, capi.E_ARG, "too small")
+    for name in (c.name for c in sc.CASES if c.refused and c.name in sc.EDGE):        # 16 pixels a side, per dimension
+        c = sc.BY_NAME[name]
+        refused(ex, sc.image(name), c.width, c.height, 1, capi.E_ARG, "too small")
+        assert ex.run(base).num_descriptors >= want - 2
     assert ex.run(base).num_descriptors >= want - 2
     refused(ex, np.zeros((20, 20, 2), np.uint8), 20, 20, 2, capi.E_ARG, "channels")
     assert ex.run(base).num_descriptors >= want - 2

@@ -2,7 +2,8 @@
 (tests/golden/surf_reference.npz) on the seeded cases of tests/surf_cases.py: the same hashes of the desaturated
 image and of the 16 response maps, bit-identical candidates, keypoints, x, y, scale and sample coordinates; bit-identical
 orientations and descriptors where this machine's C library gives the sines and cosines the fixture recorded -- and
-the comparison sees planted errors."""
+the comparison sees planted errors.  The edge cases are held to stand on the loop bounds and smallest sizes they are
+named for."""
 import numpy as np
 import pytest
 
@@ -79,6 +80,68 @@ def test_cases_show_what_they_must():
     assert len(sr.gaussian_table()[0]) == 109 and len(sr.window_starts()) == 16
 
 
+def test_edge_cases_reach_their_edges():
+    """Each case of surf_cases.EDGE stands on the loop bound it is named for: sat_rows_kernel's rounds of 256 pixels,
+    sat_cols_kernel's rounds of 8 rows, and the smallest sizes that give a response, a candidate, a descriptor."""
+    size = {n: (uc.BY_NAME[n].width, uc.BY_NAME[n].height) for n in uc.EDGE}
+    assert [size[n][0] % 256 for n in ("w256", "w512", "w513", "w769")] == [0, 0, 1, 1]
+    assert [-(-size[n][0] // 256) for n in ("w256", "w512", "w513", "w769")] == [1, 2, 3, 4]
+    assert size["tall"] == (37, 1031) and divmod(1031, 8) == (128, 7) and uc.LONG == ("tall",)
+    residues = lambda names: {uc.BY_NAME[n].height % 8 for n in names}
+    assert residues(n for n in NAMES if n not in uc.EDGE) == {0, 1, 3, 6, 7}
+    assert residues(("h42", "h44", "h45")) == {2, 4, 5} and size["h48"][1] % 8 == 0
+    assert residues(NAMES) == set(range(8))
+    # every octave that can hold a candidate at the case's size does
+    for n in uc.EDGE:
+        cand = uc.fixture(n)["candidates"]
+        for o in uc.capable_octaves(*size[n]):
+            assert (cand[:, 0] == o).any(), (n, o)
+    assert uc.capable_octaves(37, 37) == [0, 1] and uc.capable_octaves(449, 417) == [0, 1, 2, 3]
+    assert uc.capable_octaves(16, 40) == uc.capable_octaves(40, 16) == [] and uc.capable_octaves(17, 17) == [0]
+
+    # the three smallest sizes, per dimension: the case gives a first one, its image less a column or a row gives none
+    def counts(img):
+        sat = sr.integral(np.ascontiguousarray(img))
+        maps = sr.response_maps(sat)
+        cand = sr.extrema(maps)
+        kps = sr.localise(maps, cand, img.shape[1], img.shape[0])
+        return (sum(int(np.count_nonzero(m)) for o in maps for m in o), len(cand),
+                len(uc.generation_rows(sr.generate(sat, kps))))
+
+    for i, kind in enumerate(("response", "candidate", "descriptor")):
+        n = uc.SMALLEST[kind]
+        for name, cut in ((kind[:4] + "_w", np.s_[:, :-1]), (kind[:4] + "_h", np.s_[:-1, :])):
+            assert min(size[name]) == n == size[name][name.endswith("_h")], name
+            assert counts(uc.image(name))[i] >= 1 and counts(uc.image(name)[cut])[i] == 0, name
+    assert counts(uc.image("resp_w"))[1] == 0 and counts(uc.image("cand_w"))[2] == 0     # and nothing of the next kind
+    for kind, border in (("response", 5), ("candidate", 8)):
+        assert uc.SMALLEST[kind] == 2 * border + 1
+    assert uc.SMALLEST["descriptor"] == 2 * (15 * 2 + 1) + 1
+    assert sr.filter_size(0, 0) + sr.filter_size(0, 0) // 2 + 1 == 5 and sr.filter_size(0, 1) + sr.filter_size(0, 1) // 2 + 1 == 8
+
+
+def test_a_border_test_with_the_wrong_comparison_is_seen_on_the_edge_cases():
+    """x + border > w for x + border >= w keeps one sample more per row and column wherever a sample lies on the
+    bound: the maps of the planted restatement differ from the fixture's on the cases below, and on most shapes of
+    the sweep (which takes 0.5 s for its 159 shapes here, on one CPU core, so its range is not cut)."""
+    seen = []
+    for name in uc.EDGE:
+        planted = sr.response_maps(uc.restated(name)[0], plant_symmetric_border=True)
+        if [[sc.sha(m) for m in o] for o in planted] != uc.fixture(name)["map_sha"].astype(str).tolist():
+            seen.append(name)
+    assert {"w256", "w512", "w513", "w769", "tall", "resp_w", "resp_h", "cand_w", "cand_h", "desc_w", "desc_h"} <= set(seen), seen
+    shapes = uc.SWEEP_SHAPES
+    assert len(shapes) == len(set(shapes)) == 159 and sum(len(c) for c in uc.SWEEP_CHUNKS) == 159
+    assert {w for w, h in shapes if h == 80} == {h for w, h in shapes if w == 80} == set(range(1, 81))
+    differ = [s for s in shapes if uc.sweep_restated(*s) != uc.sweep_restated(*s, plant_symmetric_border=True)]
+    # every shape with any response has a sample of octave 0, sample 0 (border 5, step 1) on the bound
+    assert set(differ) == {(w, h) for w, h in shapes if min(w, h) >= uc.SMALLEST["response"] - 1}
+    empty = sc.sha(np.zeros((0, 4), np.float32))
+    assert all((dict(uc.sweep_restated(w, h))["candidates"] != empty) == (min(w, h) >= uc.SMALLEST["candidate"])
+               for w, h in shapes if min(w, h) <= uc.SMALLEST["candidate"])
+    assert len({dict(uc.sweep_restated(*s))["candidates"] for s in shapes}) > len(shapes) // 2
+
+
 def test_hand_placed_descriptors_equal_the_reference():
     fx, sat = uc.fixture("big"), uc.restated("big")[0]
     kinds = len(uc.FORCED_KINDS)
@@ -116,8 +179,12 @@ def test_planted_errors_break_an_equality():
     assert len(extra) == len(nonstrict) - len(tie_cand) == 16 and {r[3] for r in extra} == {59.0, 60.0}
     assert len(sr.localise(tie_maps, nonstrict, 161, 120)) == len(tie_fx["keypoints"]) + 4
     for other in NAMES:
-        if other != "tie":
+        if other != "tie" and other not in uc.EDGE:
             assert len(sr.extrema(uc.restated(other)[1], plant_nonstrict=True)) == len(uc.fixture(other)["candidates"])
+    # the edge cases have few blobs on a flat ground, and flat ground gives equal responses: most of them see the plant too
+    tied = [n for n in uc.EDGE if len(sr.extrema(uc.restated(n)[1], plant_nonstrict=True)) > len(uc.fixture(n)["candidates"])]
+    print("edge cases with tied neighbours:", tied)
+    assert "w256" in tied and len(tied) >= 4
 
     def oris(g):
         return np.array([r["orientation"] for r in uc.generation_rows(g)], np.float32)

@@ -6,6 +6,8 @@ reference's bytes.  Orientations and descriptors must be equal to the bytes of t
 machine's C library (the library takes atan2, sinf and cosf from the same one), and within one quantisation step of
 the fixture's.  A keypoint with an orientation sample within a few float ulps of a window bound (`ambiguous`,
 surf_restatement.orientation) is counted and left out of the byte comparisons of orientation and descriptor.
+The edge cases of surf_cases go through the same parametrised tests; a sweep of every width and height up to 80 on
+one context is held to the restatement stage by stage.
 
 On the guard: descriptor_computation's margin is 15 s + 1, its samples lie at x + 0.5, y + 0.5 for x, y in -10 .. 9,
 so a corner sample at 45 degrees is 9.5 * sqrt(2) * s = 13.44 s from the centre, a rounded coordinate at most 0.5
@@ -25,13 +27,15 @@ pytestmark = pytest.mark.gpu
 
 LIVE = [c.name for c in uc.CASES if not c.upright]
 DESCRIBED = ["base", "rgb", "many", "big", "upright", "tie"]
-MAX_W, MAX_H = 460, 420
+MAX_W, MAX_H = 770, 420
 
 
 @pytest.fixture(scope="module")
 def extractors():
     from orthosfm_amd.features import SurfExtractor
     ex = {False: SurfExtractor(0, MAX_W, MAX_H), True: SurfExtractor(0, MAX_W, MAX_H, use_upright_descriptor=1)}
+    long_w, long_h = (max(getattr(uc.BY_NAME[n], k) for n in uc.LONG) for k in ("width", "height"))
+    ex["long"] = SurfExtractor(0, long_w, long_h)          # a context of their own for the cases of 1031 rows
     yield ex
     for e in ex.values():
         e.close()
@@ -42,7 +46,7 @@ def extracted(extractors):
     """Per case what the device made of it.  Computed once; treat as read-only."""
     out = {}
     for c in uc.CASES:
-        ex = extractors[c.upright]
+        ex = extractors["long" if c.name in uc.LONG else c.upright]
         s = ex.run(uc.image(c.name))
         out[c.name] = dict(
             summary=(s.num_candidates, s.num_keypoints, s.num_descriptors, s.num_guarded, list(s.keypoints_per_octave),
@@ -75,6 +79,48 @@ def test_candidates_and_keypoints_equal_the_reference(name, extracted):
     want = uc.BY_NAME[name].counts
     if want:
         assert all(w is None or w == g for w, g in zip(want, (n_cand, n_kp, n_desc)))
+
+
+@pytest.fixture(scope="module")
+def sweep_context():
+    """One context of 80 x 80 for the whole sweep, and what it made of the 80 x 80 window of `base` before any of it."""
+    from orthosfm_amd.features import SurfExtractor
+    with SurfExtractor(0, uc.SWEEP_SIDE, uc.SWEEP_SIDE) as ex:
+        yield ex, _all_bytes(ex, sc.sweep_cut(uc.SWEEP_SIDE, uc.SWEEP_SIDE, uc.image("base")))
+
+
+def _device_stage_hashes(ex):
+    return uc.stage_hashes([[ex.debug_image(o, k) for k in range(4)] for o in range(4)], ex.debug_keypoints(False),
+                           ex.debug_keypoints(True))
+
+
+@pytest.mark.parametrize("chunk", range(len(uc.SWEEP_CHUNKS)))
+def test_sweep_equals_the_restatement(chunk, sweep_context):
+    """Every width from 1 to 80 at height 80 and every height from 1 to 80 at width 80 (no size is refused), cut from
+    one image, on one context: the 16 response maps, the candidates and the keypoints against the restatement, hashed
+    once a side.  This moves w and h across every `x + border >= w`.  The restatement takes 0.5 s for all 159 shapes (one
+    CPU core), so the range is not cut."""
+    ex = sweep_context[0]
+    for w, h in uc.SWEEP_CHUNKS[chunk]:
+        ex.run(sc.sweep_cut(w, h))
+        got, want = _device_stage_hashes(ex), uc.sweep_restated(w, h)
+        assert len(got) == len(want)
+        differ = [f"{w} x {h}: {a[0]} / {b[0]}" for a, b in zip(got, want) if a != b]
+        assert not differ, differ[:6]
+
+
+def test_sweep_leaves_nothing_behind(sweep_context):
+    """After shapes of every size on the context, the 80 x 80 window of `base` (`base` itself does not fit a context of
+    80 x 80) gives its earlier bytes, which are the restatement's: nothing depends on the image that was there before."""
+    ex, before = sweep_context
+    window = sc.sweep_cut(uc.SWEEP_SIDE, uc.SWEEP_SIDE, uc.image("base"))
+    for w, h in ((1, 80), (80, 1), (80, 80), (33, 80)):
+        ex.run(sc.sweep_cut(w, h))
+        assert _all_bytes(ex, window) == before
+    maps = sr.response_maps(sr.integral(window))
+    cand = sr.extrema(maps)
+    assert _device_stage_hashes(ex) == uc.stage_hashes(maps, cand, sr.localise(maps, cand, uc.SWEEP_SIDE, uc.SWEEP_SIDE))
+    assert len(cand) > 0
 
 
 def test_tied_maxima_are_rejected(extracted):

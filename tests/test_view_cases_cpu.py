@@ -9,7 +9,8 @@ import view_cases as vc
 def test_the_fixture_holds_every_shape():
     shapes = {(a.shape[1], a.shape[0], 1 if a.ndim == 2 else a.shape[2]) for a in vc.halve_images().values()}
     assert set(vc.HALVE_SHAPES) <= shapes
-    assert set(vc.halve_images()) | {"refused"} == set(vc.golden())
+    chains = {vc.chain_name(w, h, k) for w, h, n in vc.HALVE_CHAINS for k in range(1, n + 1)}
+    assert set(vc.halve_images()) | chains | {"refused"} == set(vc.golden())
 
 
 @pytest.mark.parametrize("name", sorted(vc.halve_images()))
@@ -18,6 +19,48 @@ def test_restatement_equals_the_reference(name):
     got = vc.halve(img)
     assert got.shape == want.shape == (((img.shape[0] + 1) >> 1, (img.shape[1] + 1) >> 1) + img.shape[2:])
     assert got.tobytes() == want.tobytes()
+
+
+def test_the_grey8_shapes_stand_on_the_kernels_edges():
+    """halve_grey8_kernel (grey, w % 8 == 0; a thread per 8 source bytes of two rows, 256 threads a workgroup): even and
+    odd heights, one quad per row, a work count over two workgroups that is no multiple of 256."""
+    work = {(w, h): (w // 8) * ((h + 1) >> 1) for w, h, c in vc.GREY8_SHAPES}
+    assert all(vc.takes_grey8(w, c) for w, h, c in vc.GREY8_SHAPES) and not vc.takes_grey8(8, 3) and not vc.takes_grey8(132, 1)
+    assert work[8, 2] == 1 and work[8, 3] == 2                                     # w == 8: one quad per row
+    assert {h % 2 for w, h, c in vc.GREY8_SHAPES} == {0, 1}
+    assert sum(h % 2 for w, h, c in vc.GREY8_SHAPES) >= 5                          # y1 = min(2y + 1, h - 1) clamps
+    assert work[72, 57] == 261 and 256 < work[72, 57] < 512 and work[72, 57] % 256 == 5
+    assert work[64, 64] == 256 and work[264, 3] == 66
+
+
+def test_chains_equal_the_reference_step_by_step():
+    """Every step of the grey chains against the reference halving its own last result, and the kernel each step takes."""
+    taken = {}
+    for (w, h, n), img in vc.chain_images().items():
+        assert img.shape == (h, w)
+        for step in range(1, n + 1):
+            taken.setdefault((w, h), []).append(vc.takes_grey8(img.shape[1], 1))
+            img = vc.halve(img)
+            want = vc.golden()[vc.chain_name(w, h, step)]
+            assert img.shape == want.shape and img.tobytes() == want.tobytes(), (w, h, step)
+        assert vc.chain(vc.chain_images()[w, h, n], n + 1, 0)[1].tobytes() == img.tobytes()
+    assert taken[72, 57] == [True, False, False]          # 72 -> 36 -> 18 -> 9
+    assert taken[132, 80] == [False, False, False]        # 132 -> 66 -> 33 -> 17
+    assert taken[143, 10] == [False, True, False]         # 143 -> 72 (5 high: odd) -> 36 -> 18
+    assert vc.golden()[vc.chain_name(132, 80, 3)].shape == (10, 17) and vc.golden()[vc.chain_name(143, 10, 1)].shape == (5, 72)
+
+
+def test_the_golden_sees_a_dropped_last_row():
+    """A halving that does not repeat the last row of an odd height (it takes the row above instead) differs from the
+    reference on every new shape of odd height, on both kernels' shapes, and on the 8-byte step of a chain."""
+    seen = {name for name, img in vc.halve_images().items()
+            if vc.halve(img, plant_drop_last_row=True).tobytes() != vc.golden()[name].tobytes()}
+    odd = {f"random_{w}x{h}x{c}" for w, h, c in vc.HALVE_SHAPES if h % 2}
+    assert seen == odd                                     # all255_5x7x3 is odd too, and cannot show it
+    assert {"random_8x3x1", "random_16x5x1", "random_24x7x1", "random_72x57x1", "random_264x3x1"} <= seen
+    step1 = vc.halve(vc.chain_images()[143, 10, 3])
+    assert step1.shape == (5, 72)
+    assert vc.halve(step1, plant_drop_last_row=True).tobytes() != vc.golden()[vc.chain_name(143, 10, 2)].tobytes()
 
 
 def test_the_cases_hold_every_remainder_and_the_top_of_the_range():

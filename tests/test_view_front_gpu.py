@@ -85,11 +85,29 @@ def test_chains_equal_the_restatement():
             s = front.load(img)
             assert s.num_halvings == n and (s.import_width, s.import_height) == (imported.shape[1], imported.shape[0]), kw
             assert front.debug_image().tobytes() == feat.tobytes() and front.debug_image().shape == feat.shape, kw
-    # a grey chain of two halvings: the 8-byte path, then the general one (32 wide, then 16)
+    # a grey chain of two halvings, 64 wide, then 32: the 8-byte path both times (32 is a multiple of 8 as well)
     grey = vc.halve_images()["patches_64x64x1"]
+    assert vc.takes_grey8(64, 1) and vc.takes_grey8(32, 1)
     with ViewFrontEnd(0, 64, 64, downscale_factor=3, max_image_size=0, feature_types=capi.FEATURE_SURF) as front:
         front.load(grey)
         assert front.debug_image().tobytes() == vc.chain(grey, 3, 0)[1].tobytes()
+
+
+@pytest.mark.parametrize("chain", vc.HALVE_CHAINS, ids=lambda c: f"{c[0]}x{c[1]}")
+def test_grey_chains_equal_the_reference_at_every_step(chain):
+    """Chains in which the 8-byte kernel is followed by the general one, follows it, and is not taken at all: every
+    step (a front end that stops there) against the reference halving its own last result."""
+    from orthosfm_amd import capi
+    from orthosfm_amd.features import ViewFrontEnd
+    w, h, n = chain
+    img = vc.chain_images()[chain]
+    for step in range(1, n + 1):
+        want = vc.golden()[vc.chain_name(w, h, step)]
+        with ViewFrontEnd(0, w, h, downscale_factor=step + 1, max_image_size=0, feature_types=capi.FEATURE_SURF) as front:
+            s = front.load(img)
+            got = front.debug_image()
+            assert (s.num_halvings, s.feature_width, s.feature_height) == (step, want.shape[1], want.shape[0]), step
+            assert got.shape == want.shape and got.tobytes() == want.tobytes(), step
 
 
 # ---- 2. hand-off kernels on hostile values ----------------------------------------------------------------------

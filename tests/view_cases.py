@@ -18,7 +18,15 @@ from orthosfm_amd import synth
 STREAM = 0x71E3 << 16
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "halve_reference.npz")
 
-HALVE_SHAPES = [(2, 2, 1), (3, 2, 1), (2, 3, 3), (5, 7, 3), (64, 64, 1), (65, 63, 3), (257, 190, 1)]   # (w, h, c)
+HALVE_SHAPES = [(2, 2, 1), (3, 2, 1), (2, 3, 3), (5, 7, 3), (64, 64, 1), (65, 63, 3), (257, 190, 1),          # (w, h, c)
+                # halve_grey8_kernel (grey, w % 8 == 0) on its edges: one quad per row at even and odd height, odd
+                # heights at 2 and 3 quads, 9 x 29 = 261 work items (two workgroups, the second all but empty), 33 quads
+                (8, 2, 1), (8, 3, 1), (16, 5, 1), (24, 7, 1), (72, 57, 1), (264, 3, 1)]
+GREY8_SHAPES = [s for s in HALVE_SHAPES if s[2] == 1 and s[0] % 8 == 0]
+# grey chains (w, h, halvings), every step of which is in the fixture: 72 -> 36 -> 18 -> 9 (the 8-byte kernel, then the
+# general one twice), 132 -> 66 -> 33 -> 17 (the general one throughout) and 143 -> 72 -> 36 -> 18 (general, 8-byte at
+# an odd height, general)
+HALVE_CHAINS = [(72, 57, 3), (132, 80, 3), (143, 10, 3)]
 REFUSED_SHAPE = (1, 5, 1)
 
 
@@ -50,15 +58,35 @@ def halve_images():
     return out
 
 
+def chain_name(w, h, step):
+    return f"chain_{w}x{h}_step{step}"
+
+
+@lru_cache(maxsize=None)
+def chain_images():
+    """(w, h, halvings) -> the seeded random grey image a chain of HALVE_CHAINS starts from."""
+    out = {}
+    for i, (w, h, n) in enumerate(HALVE_CHAINS):
+        out[w, h, n] = _random_image(w, h, 1, 51 + i)
+        out[w, h, n].setflags(write=False)
+    return out
+
+
+def takes_grey8(w, c):
+    """launch_halve's choice of kernel."""
+    return c == 1 and w % 8 == 0
+
+
 @lru_cache(maxsize=None)
 def golden():
     z = np.load(GOLDEN)
     return {k: z[k] for k in z.files}
 
 
-def halve(img, round_down=False):
+def halve(img, round_down=False, plant_drop_last_row=False):
     """rescale_half_size<uint8_t>: (w + 1) >> 1 by (h + 1) >> 1, the last column / row replicated for odd sizes, a
-    pixel (uchar)(0.25f a + 0.25f b + 0.25f c + 0.25f d + 0.5f) in float32.  round_down: a planted error (no + 0.5f)."""
+    pixel (uchar)(0.25f a + 0.25f b + 0.25f c + 0.25f d + 0.5f) in float32.  round_down: a planted error (no + 0.5f);
+    plant_drop_last_row: another (at an odd height the last row is not repeated: the row above takes its place)."""
     img = np.asarray(img)
     h, w = img.shape[:2]
     if w < 2 or h < 2:
@@ -66,6 +94,8 @@ def halve(img, round_down=False):
     ow, oh = (w + 1) >> 1, (h + 1) >> 1
     x0, y0 = 2 * np.arange(ow), 2 * np.arange(oh)
     x1, y1 = np.minimum(x0 + 1, w - 1), np.minimum(y0 + 1, h - 1)
+    if plant_drop_last_row and h % 2:
+        y1[-1] = h - 2
     f = img.astype(np.float32)
     q = np.float32(0.25)
     v = q * f[y0][:, x0]
