@@ -164,11 +164,16 @@ int osfm_match_create(int device, int num_views, const osfm_match_options *opts,
     }
     // at most 512: the finish kernel's scan of the special rows keys them with nine bits
     if (m->opts.special_kernel_max != 0) m->special_max = std::min(std::max(m->opts.special_kernel_max, 0), 512);
+    // The finish kernel skips work for a query whose ratio test fails against a lower bound of its second best
+    // (match_finish_kernel): that needs thresholds that never rise as the second distance falls.
+    const auto monotone = [](const std::vector<int32_t> &tab) { return std::is_sorted(tab.begin(), tab.end()); };
     std::vector<int32_t> t;
     build_lowe_table(m->opts.sift_lowe_ratio, false, &t);
+    if (!monotone(t)) { set_error("match_create: the SIFT ratio table is not monotone"); return OSFM_E_ARG; }
     OSFM_RETURN_IF(m->lowe_sift.reserve(t.size() * 4));
     OSFM_HIP_CHECK(hipMemcpy(m->lowe_sift.ptr, t.data(), t.size() * 4, hipMemcpyHostToDevice));
     build_lowe_table(m->opts.surf_lowe_ratio, true, &t);
+    if (!monotone(t)) { set_error("match_create: the SURF ratio table is not monotone"); return OSFM_E_ARG; }
     OSFM_RETURN_IF(m->lowe_surf.reserve(t.size() * 4));
     OSFM_HIP_CHECK(hipMemcpy(m->lowe_surf.ptr, t.data(), t.size() * 4, hipMemcpyHostToDevice));
     m->tab_sift.reject_from = m->lowe_sift.as<int32_t>();

@@ -803,19 +803,18 @@ void launch_match_tiles(int ch, bool masked, bool any_special, bool any_c0, bool
 // The reference's state starts at (0, 0, idx 0): best = max(0, ip1),
 // second = max(0, ip2), index = idx1 if ip1 >= 0 else 0.
 // ---------------------------------------------------------------------------
+// the reference's clamped squared distance of an inner product: even, 0 .. 65534, never rising with ip
+__device__ __forceinline__ int match_distance(int ip, const LoweTable &tab)
+{
+    const int b = max(ip, 0);
+    return tab.is_signed ? 32258 - 2 * min(b, 16129) : min(32767, 65025 - min(b, 65025)) * 2;
+}
+
 __device__ __forceinline__ int
 accept_match(int ip1, int ip2, int idx1, const LoweTable &tab)
 {
-    int b = max(ip1, 0), s = max(ip2, 0);
     const int idx = ip1 >= 0 ? idx1 : 0;
-    int d1, d2;
-    if (tab.is_signed) {
-        b = min(b, 16129); s = min(s, 16129);
-        d1 = 32258 - 2 * b; d2 = 32258 - 2 * s;
-    } else {
-        b = min(b, 65025); s = min(s, 65025);
-        d1 = min(32767, 65025 - b) * 2; d2 = min(32767, 65025 - s) * 2;
-    }
+    const int d1 = match_distance(ip1, tab), d2 = match_distance(ip2, tab);
     if (d1 > tab.max_d1) return -1;
     if (d1 >= tab.reject_from[d2 >> 1]) return -1;
     return idx;
@@ -1010,243 +1009,268 @@ scan_specials(const MatchProblem &pd, int dir, int q, int lane, int &best_out, i
 #define OSFM_FINISH_BATCH 16
 #endif
 
+// A workgroup of the finish kernel owns a span of kFinishSpan consecutive queries of one problem and one direction;
+// a lane takes the queries j * kFinishThreads + threadIdx.x of the span one after the other, so the loads of a turn
+// coalesce as with one query per lane.  (One query per lane in workgroups of 128 made 128 112 workgroups of a
+// 408-pair launch, half of them one 16-byte load and a test long; spans of 1024 take 0.05 - 0.07 ms off such a
+// launch and add 0.04 ms to the low-res launch, whose lists are half a span: DESIGN 2.3, round 10.)
+constexpr int kFinishThreads = 256, kFinishTurns = 4, kFinishSpan = kFinishThreads * kFinishTurns;
+
 template <int DIM, bool SIGNED>
-__global__ __launch_bounds__(128) void
+__global__ __launch_bounds__(kFinishThreads) void
 match_finish_kernel(const MatchProblem *__restrict__ problems, const RowPart *__restrict__ rowparts,
     const ColPart *__restrict__ colparts, const RowPart *__restrict__ sp_parts, const int32_t *__restrict__ sp_col,
     LoweTable tab, int force_exact, ExactItem *__restrict__ exact_items, int32_t *__restrict__ exact_count, int exact_cap,
-    int32_t *__restrict__ rs_count, RescoreItem *__restrict__ rs_items, int blocks_per_dir, int total_blocks)
+    int32_t *__restrict__ rs_count, RescoreItem *__restrict__ rs_items, int spans_per_dir, int total_blocks)
 {
     // every XCD works through a contiguous run of problems, so the descriptors the
     // rescans gather from are fetched into one L2 instead of all eight
     const int lin = xcd_remap(blockIdx.x, total_blocks);
-    const int problem = lin / (2 * blocks_per_dir), within = lin - problem * 2 * blocks_per_dir;
+    const int problem = lin / (2 * spans_per_dir), within = lin - problem * 2 * spans_per_dir;
     const MatchProblem &pd = problems[problem];
-    const int dir = within / blocks_per_dir;
-    const int block_x = within - dir * blocks_per_dir;
-    const int q = block_x * blockDim.x + threadIdx.x;
+    const int dir = within / spans_per_dir;
+    const int span = within - dir * spans_per_dir;
     const int lane = threadIdx.x & 63;
     const int nq = dir == 0 ? pd.n1 : pd.n2;
     const int nc = dir == 0 ? pd.n2 : pd.n1;
-    if ((int)(block_x * blockDim.x) >= nq) return;    // whole block out of range
     int32_t *out = dir == 0 ? pd.m12 : pd.m21;
-    const bool active = q < nq;
-
-    // ip1 / idx1: exact best; ip2: second largest GROUP best (lower bound of the
-    // true second); code: group of the best (dir 1), idx1 = its row block there
-    // kind1 = 3: a special query: (ip1, idx1) = the largest stream maximum of match_special_kernel and the
-    // first column of that stream (its 32 candidates follow at a stride of 128), ip2 the second largest
-    // stream maximum
-    int ip1 = INT_MIN, ip2 = INT_MIN, idx1 = 0, code = 0, kind1 = 0;
-    // Problems whose special descriptors went through match_special_kernel (pd.sp): a special
-    // query takes its result from there (one partial per chunk of candidates); any other query
-    // merges the tile kernel's partials below and then the largest inner product over the OTHER
-    // set's special descriptors, which the tile kernel saw as blanks.
-    int sp_slot = -1;
-    if (active && nc > 0 && pd.sp) {
-        const int ns_mine = dir == 0 ? pd.nsA : pd.nsB;
-        if (ns_mine > 0) sp_slot = (dir == 0 ? pd.special_slot : pd.special_slot_B)[q];
-        if (sp_slot >= 0) {
-            const int ns_pad = (ns_mine + 31) & ~31;
-            const int chunk_cols = pd.sp_wide[dir] ? kSpWideChunk : kSpChunk;
-            const int nchunk = (nc + chunk_cols - 1) / chunk_cols;
-            const RowPart *rp0 = sp_parts + pd.sp_row_off[dir] + sp_slot;
-            for (int c = 0; c < nchunk; ++c) {
-                const RowPart p = rp0[(int64_t)c * ns_pad];
-                ip2 = max(max(ip2, p.ip_second), min(ip1, p.ip_best));
-                if (p.ip_best >= ip1 && p.ip_best != INT_MIN) { ip1 = p.ip_best; idx1 = p.idx_best; }   // later chunk wins ties
-            }
-            kind1 = pd.sp_wide[dir] ? 4 : 3;
-        }
-    }
-    // an ordinary query whose best candidate is (or ties with) a special descriptor of the other set:
-    // sp_m1 = the best of the ordinary candidates (exact value), the special ones are scanned below
-    bool sp_scan = false;
-    int sp_m1 = INT_MIN;
-    if (active && nc > 0 && sp_slot < 0) {
-        if (dir == 0) {
-            const int64_t stride = (int64_t)pd.nrb * kRowsPerBlock;
-            // special rows keep their partials behind the main row blocks
-            int slot = q;
-            if (pd.special_slot && !pd.sp) {
-                const int sidx = pd.special_slot[q];
-                if (sidx >= 0) slot = pd.nrb_main * kRowsPerBlock + sidx;
-            }
-            // four segments per round, loads issued together (see the column side below)
-            constexpr int kBatch = 4;
-            const RowPart *rp0 = rowparts + pd.rowpart_off + slot;
-            const int nseg = pd.nseg;
-            for (int s0 = 0; s0 < nseg; s0 += kBatch) {
-                RowPart p[kBatch];
-#pragma unroll
-                for (int u = 0; u < kBatch; ++u) p[u] = rp0[(int64_t)min(s0 + u, nseg - 1) * stride];
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int u = 0; u < kBatch; ++u) {
-                    const bool live = s0 + u < nseg;
-                    const int pb = live ? p[u].ip_best : INT_MIN, ps = live ? p[u].ip_second : INT_MIN;
-                    // later segment wins ties (its columns have larger indices)
-                    ip2 = max(max(ip2, ps), min(ip1, pb));
-                    if (pb >= ip1 && pb != INT_MIN) { ip1 = pb; idx1 = p[u].idx_best; kind1 = p[u].pad; }
-                }
-            }
-        } else {
-            // The column partials are two planes (store_colpart); only the best keys are streamed.  Sixteen row
-            // blocks per round, their loads issued together (left as a plain loop the compiler emits load, wait,
-            // fold per row block: one memory latency per partial with a single request in flight per lane).
-            // Why the second keys of all row blocks but the winning one are not needed: the merged second is
-            // max(second of the winner, best of every other block) -- a block's second key is never above its
-            // best key, and the fold takes in the best of every block that does not win in the end: on arrival
-            // if it loses there (min(ip1, pb) = pb), and when it is overtaken if it led for a while (pb >= ip1,
-            // so min(ip1, pb) = the displaced ip1).  Both bound that block's second from above.
-            constexpr int kBatch = OSFM_FINISH_BATCH;
-            const int32_t *best0 = reinterpret_cast<const int32_t *>(colparts + pd.colpart_off) + q;
-            const int nrb = pd.nrb;
-            const int64_t stride = pd.n2stride;
-            for (int rb0 = 0; rb0 < nrb; rb0 += kBatch) {
-                int kb[kBatch];
-#pragma unroll
-                for (int u = 0; u < kBatch; ++u)
-                    // (read once, 2.5 GB of them per launch: non-temporal, so that they do not push the descriptors
-                    //  the rescans gather out of the L2)
-                    kb[u] = __builtin_nontemporal_load(best0 + (int64_t)min(rb0 + u, nrb - 1) * stride);     // clamped repeats are not folded
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int u = 0; u < kBatch; ++u) {
-                    // no branch (a branch would let the optimiser sink each load to its use)
-                    const bool live = rb0 + u < nrb;
-                    const int pb = (!live || kb[u] == kKeyNone) ? INT_MIN : (kb[u] >> 8);
-                    ip2 = max(ip2, min(ip1, pb));
-                    if (pb >= ip1 && pb != INT_MIN) { ip1 = pb; idx1 = rb0 + u; code = kb[u] & 255; }      // later block wins ties
-                }
-            }
-            // the winner's second key: one gathered entry of the second plane, right behind the best plane
-            if (ip1 != INT_MIN) {
-                const int ks = __builtin_nontemporal_load(best0 + ((int64_t)nrb + idx1) * stride);
-                ip2 = max(ip2, ks == kKeyNone ? INT_MIN : (ks >> 8));
-            }
-        }
-        if (pd.sp && (dir == 0 ? pd.nsB : pd.nsA) > 0) {
-            // the other set's special descriptors as candidates of this query: their largest inner product
-            const int t1 = sp_col[pd.sp_col_off[dir ^ 1] + q];
-            if (t1 >= ip1 && t1 != INT_MIN) {
-                // the best is a special descriptor (or ties with one): which one, and the second best among
-                // them, is found by scanning them -- only if the ratio test can still pass (the best of the
-                // ordinary candidates, an exact score or a blank's 0, bounds the second best from below)
-                sp_m1 = ip1; ip1 = t1; sp_scan = true;
-            } else {
-                ip2 = max(ip2, t1);
-            }
-        }
-    }
     const int limit = tab.is_signed ? 32767 : 65535;
-    bool exact = active && nc > 0 && (force_exact || pd.force_exact || ip1 > limit);
-    bool refine = false;
-    int res = -1;
-    if (active && nc > 0 && !exact) {
-        // optimistic test against the lower bound of the second best
-        res = accept_match(ip1, sp_scan ? max(sp_m1, ip2) : ip2, 0, tab);
-        if (res >= 0) {
-            if (ip1 < 0) { res = 0; sp_scan = false; }   // reference state (0, 0, idx 0): nothing to refine
-            else if ((sp_scan ? sp_m1 : ip2) == ip1) { exact = true; sp_scan = false; }   // accepted despite a tie for best
-                                                // (NaN accept / ratio >= 1): defer to the sequential-scan kernel
-            else if (!sp_scan) refine = true;
+    // a span wholly past nq does nothing; the turns are not unrolled (the rescans are long), their ballots are per turn
+#pragma unroll 1
+    for (int q0 = span * kFinishSpan; q0 < min(nq, (span + 1) * kFinishSpan); q0 += kFinishThreads) {
+        const int q = q0 + (int)threadIdx.x;
+        const bool active = q < nq;
+
+        // ip1 / idx1: exact best; ip2: second largest GROUP best (lower bound of the
+        // true second); code: group of the best (dir 1), idx1 = its row block there
+        // kind1 = 3: a special query: (ip1, idx1) = the largest stream maximum of match_special_kernel and the
+        // first column of that stream (its 32 candidates follow at a stride of 128), ip2 the second largest
+        // stream maximum
+        int ip1 = INT_MIN, ip2 = INT_MIN, idx1 = 0, code = 0, kind1 = 0;
+        // Problems whose special descriptors went through match_special_kernel (pd.sp): a special
+        // query takes its result from there (one partial per chunk of candidates); any other query
+        // merges the tile kernel's partials below and then the largest inner product over the OTHER
+        // set's special descriptors, which the tile kernel saw as blanks.
+        int sp_slot = -1;
+        if (active && nc > 0 && pd.sp) {
+            const int ns_mine = dir == 0 ? pd.nsA : pd.nsB;
+            if (ns_mine > 0) sp_slot = (dir == 0 ? pd.special_slot : pd.special_slot_B)[q];
+            if (sp_slot >= 0) {
+                const int ns_pad = (ns_mine + 31) & ~31;
+                const int chunk_cols = pd.sp_wide[dir] ? kSpWideChunk : kSpChunk;
+                const int nchunk = (nc + chunk_cols - 1) / chunk_cols;
+                const RowPart *rp0 = sp_parts + pd.sp_row_off[dir] + sp_slot;
+                for (int c = 0; c < nchunk; ++c) {
+                    const RowPart p = rp0[(int64_t)c * ns_pad];
+                    ip2 = max(max(ip2, p.ip_second), min(ip1, p.ip_best));
+                    if (p.ip_best >= ip1 && p.ip_best != INT_MIN) { ip1 = p.ip_best; idx1 = p.idx_best; }   // later chunk wins ties
+                }
+                kind1 = pd.sp_wide[dir] ? 4 : 3;
+            }
+        }
+        // an ordinary query whose best candidate is (or ties with) a special descriptor of the other set:
+        // sp_m1 = the best of the ordinary candidates (exact value), the special ones are scanned below
+        bool sp_scan = false;
+        bool failed = false;        // the optimistic test below has been made already, and has failed
+        int sp_m1 = INT_MIN;
+        if (active && nc > 0 && sp_slot < 0) {
+            if (dir == 0) {
+                const int64_t stride = (int64_t)pd.nrb * kRowsPerBlock;
+                // special rows keep their partials behind the main row blocks
+                int slot = q;
+                if (pd.special_slot && !pd.sp) {
+                    const int sidx = pd.special_slot[q];
+                    if (sidx >= 0) slot = pd.nrb_main * kRowsPerBlock + sidx;
+                }
+                // four segments per round, loads issued together (see the column side below)
+                constexpr int kBatch = 4;
+                const RowPart *rp0 = rowparts + pd.rowpart_off + slot;
+                const int nseg = pd.nseg;
+                for (int s0 = 0; s0 < nseg; s0 += kBatch) {
+                    RowPart p[kBatch];
+#pragma unroll
+                    for (int u = 0; u < kBatch; ++u) p[u] = rp0[(int64_t)min(s0 + u, nseg - 1) * stride];
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int u = 0; u < kBatch; ++u) {
+                        const bool live = s0 + u < nseg;
+                        const int pb = live ? p[u].ip_best : INT_MIN, ps = live ? p[u].ip_second : INT_MIN;
+                        // later segment wins ties (its columns have larger indices)
+                        ip2 = max(max(ip2, ps), min(ip1, pb));
+                        if (pb >= ip1 && pb != INT_MIN) { ip1 = pb; idx1 = p[u].idx_best; kind1 = p[u].pad; }
+                    }
+                }
+            } else {
+                // The column partials are two planes (store_colpart); only the best keys are streamed.  Sixteen row
+                // blocks per round, their loads issued together (left as a plain loop the compiler emits load, wait,
+                // fold per row block: one memory latency per partial with a single request in flight per lane).
+                // Why the second keys of all row blocks but the winning one are not needed: the merged second is
+                // max(second of the winner, best of every other block) -- a block's second key is never above its
+                // best key, and the fold takes in the best of every block that does not win in the end: on arrival
+                // if it loses there (min(ip1, pb) = pb), and when it is overtaken if it led for a while (pb >= ip1,
+                // so min(ip1, pb) = the displaced ip1).  Both bound that block's second from above.
+                constexpr int kBatch = OSFM_FINISH_BATCH;
+                const int32_t *best0 = reinterpret_cast<const int32_t *>(colparts + pd.colpart_off) + q;
+                const int nrb = pd.nrb;
+                const int64_t stride = pd.n2stride;
+                for (int rb0 = 0; rb0 < nrb; rb0 += kBatch) {
+                    int kb[kBatch];
+#pragma unroll
+                    for (int u = 0; u < kBatch; ++u)
+                        // (read once, 2.5 GB of them per launch: non-temporal, so that they do not push the descriptors
+                        //  the rescans gather out of the L2)
+                        kb[u] = __builtin_nontemporal_load(best0 + (int64_t)min(rb0 + u, nrb - 1) * stride);     // clamped repeats are not folded
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int u = 0; u < kBatch; ++u) {
+                        // no branch (a branch would let the optimiser sink each load to its use)
+                        const bool live = rb0 + u < nrb;
+                        const int pb = (!live || kb[u] == kKeyNone) ? INT_MIN : (kb[u] >> 8);
+                        ip2 = max(ip2, min(ip1, pb));
+                        if (pb >= ip1 && pb != INT_MIN) { ip1 = pb; idx1 = rb0 + u; code = kb[u] & 255; }      // later block wins ties
+                    }
+                }
+                // The winner's second key: one gathered entry of the second plane, right behind the best plane -- a
+                // request of its own per column, issued only where its value can be used.  The ratio test is monotone
+                // in the second best: accept_match rejects iff d1 > max_d1 (no second in it) or d1 >= reject_from[d2 / 2];
+                // d2 never rises with the second (match_distance), and reject_from never rises as d2 falls
+                // (build_lowe_table: the first even d1 with float(d1) / float(d2) > lowe^2, a correctly rounded
+                // quotient that only grows as d2 falls; d2 = 0 holds 2, the least any entry can; match_create checks that
+                // the table is sorted).  So a column that fails against the fold's lower bound fails against the full
+                // second too, and then nothing reads its second: res stays -1, `exact` is set only behind res >= 0,
+                // no RescoreItem is written.  Two thirds of the headline set's columns end here.
+                // Kept unconditional: the wrap-exact path (force_exact, ip1 > limit) and problems whose other set has
+                // special descriptors (their largest inner product joins the test below).
+                if (!(force_exact || pd.force_exact || ip1 > limit || (pd.sp && pd.nsA > 0))) {
+                    const int d1 = match_distance(ip1, tab);
+                    failed = d1 > tab.max_d1 || d1 >= tab.reject_from[match_distance(ip2, tab) >> 1];
+                }
+                if (ip1 != INT_MIN && !failed) {
+                    const int ks = __builtin_nontemporal_load(best0 + ((int64_t)nrb + idx1) * stride);
+                    ip2 = max(ip2, ks == kKeyNone ? INT_MIN : (ks >> 8));
+                }
+            }
+            if (pd.sp && (dir == 0 ? pd.nsB : pd.nsA) > 0) {
+                // the other set's special descriptors as candidates of this query: their largest inner product
+                const int t1 = sp_col[pd.sp_col_off[dir ^ 1] + q];
+                if (t1 >= ip1 && t1 != INT_MIN) {
+                    // the best is a special descriptor (or ties with one): which one, and the second best among
+                    // them, is found by scanning them -- only if the ratio test can still pass (the best of the
+                    // ordinary candidates, an exact score or a blank's 0, bounds the second best from below)
+                    sp_m1 = ip1; ip1 = t1; sp_scan = true;
+                } else {
+                    ip2 = max(ip2, t1);
+                }
+            }
+        }
+        bool exact = active && nc > 0 && (force_exact || pd.force_exact || ip1 > limit);
+        bool refine = false;
+        int res = -1;
+        if (active && nc > 0 && !exact) {
+            // optimistic test against the lower bound of the second best
+            res = failed ? -1 : accept_match(ip1, sp_scan ? max(sp_m1, ip2) : ip2, 0, tab);
+            if (res >= 0) {
+                if (ip1 < 0) { res = 0; sp_scan = false; }   // reference state (0, 0, idx 0): nothing to refine
+                else if ((sp_scan ? sp_m1 : ip2) == ip1) { exact = true; sp_scan = false; }   // accepted despite a tie for best
+                                                    // (NaN accept / ratio >= 1): defer to the sequential-scan kernel
+                else if (!sp_scan) refine = true;
+            } else {
+                sp_scan = false;
+            }
         } else {
             sp_scan = false;
         }
-    } else {
-        sp_scan = false;
-    }
-    // The groups of the raw tile kernels go to the bucketed rescoring (match_rescore_kernel, which
-    // writes the result) while their bucket has room; everything else is rescanned here.
-    bool deferred = false;
-    if (!SIGNED && DIM == 128 && rs_count != nullptr && refine) {
-        int b = -1, sub = 0, cap = 0;
-        int64_t item = 0;
-        const int nb1 = pd.nrb_main * 4;
-        if (dir == 1) {
-            if (kind1 == 0 && idx1 < pd.nrb_main && code < 8) {
-                b = idx1 * 4 + (code >> 1); sub = code & 1;
-                item = (int64_t)b * kRescoreCap1; cap = kRescoreCap1;
+        // The groups of the raw tile kernels go to the bucketed rescoring (match_rescore_kernel, which
+        // writes the result) while their bucket has room; everything else is rescanned here.
+        bool deferred = false;
+        if (!SIGNED && DIM == 128 && rs_count != nullptr && refine) {
+            int b = -1, sub = 0, cap = 0;
+            int64_t item = 0;
+            const int nb1 = pd.nrb_main * 4;
+            if (dir == 1) {
+                if (kind1 == 0 && idx1 < pd.nrb_main && code < 8) {
+                    b = idx1 * 4 + (code >> 1); sub = code & 1;
+                    item = (int64_t)b * kRescoreCap1; cap = kRescoreCap1;
+                }
+            } else if (kind1 == 1) {
+                const int tq = idx1 >> 6;        // the group's first tile
+                if (tq < (pd.n2 + kTileCols - 1) / kTileCols) {
+                    const int w = tq / kRescoreWin, k = w * 32 + (idx1 & 31);
+                    b = nb1 + k; sub = tq - w * kRescoreWin;
+                    item = (int64_t)nb1 * kRescoreCap1 + (int64_t)k * kRescoreCap0; cap = kRescoreCap0;
+                }
             }
-        } else if (kind1 == 1) {
-            const int tq = idx1 >> 6;        // the group's first tile
-            if (tq < (pd.n2 + kTileCols - 1) / kTileCols) {
-                const int w = tq / kRescoreWin, k = w * 32 + (idx1 & 31);
-                b = nb1 + k; sub = tq - w * kRescoreWin;
-                item = (int64_t)nb1 * kRescoreCap1 + (int64_t)k * kRescoreCap0; cap = kRescoreCap0;
-            }
-        }
-        if (b >= 0) {
-            const int slot = atomicAdd(rs_count + pd.rs_bucket_off + b, 1);
-            if (slot < cap) {
-                RescoreItem it;
-                it.q_sub = q * 32 + sub; it.ip2 = ip2;
-                rs_items[pd.rs_item_off + item + slot] = it;
-                refine = false; deferred = true;
+            if (b >= 0) {
+                const int slot = atomicAdd(rs_count + pd.rs_bucket_off + b, 1);
+                if (slot < cap) {
+                    RescoreItem it;
+                    it.q_sub = q * 32 + sub; it.ip2 = ip2;
+                    rs_items[pd.rs_item_off + item + slot] = it;
+                    refine = false; deferred = true;
+                }
             }
         }
-    }
-    // Queries that pass get their best group re-scored, one query at a time by
-    // the whole wave.  The rescan also yields the exact best of the group: it
-    // differs from ip1 only when ip1 = 0 came from a padding column (raw path),
-    // i.e. when no real candidate reaches 0 -- then it is the value to test.
-    unsigned long long todo = __ballot(refine);
-    int rbest = 0, rsecond = 0, ridx = 0;
-    while (todo) {
-        int src[2], qs[2], is[2], cs[2], ks[2], idx[2], found[2], second[2];
-        src[0] = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        src[1] = todo ? __ffsll((long long)todo) - 1 : src[0];     // odd count: the last one twice
-        todo &= todo - 1;
+        // Queries that pass get their best group re-scored, one query at a time by
+        // the whole wave.  The rescan also yields the exact best of the group: it
+        // differs from ip1 only when ip1 = 0 came from a padding column (raw path),
+        // i.e. when no real candidate reaches 0 -- then it is the value to test.
+        unsigned long long todo = __ballot(refine);
+        int rbest = 0, rsecond = 0, ridx = 0;
+        while (todo) {
+            int src[2], qs[2], is[2], cs[2], ks[2], idx[2], found[2], second[2];
+            src[0] = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            src[1] = todo ? __ffsll((long long)todo) - 1 : src[0];     // odd count: the last one twice
+            todo &= todo - 1;
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            qs[u] = __builtin_amdgcn_readlane(q, src[u]);
-            is[u] = __builtin_amdgcn_readlane(idx1, src[u]);
-            cs[u] = __builtin_amdgcn_readlane(code, src[u]);
-            ks[u] = __builtin_amdgcn_readlane(kind1, src[u]);
-        }
-        if (dir == 0) rescan_groups<DIM, 0>(pd, qs, is, cs, ks, lane, idx, found, second);
-        else rescan_groups<DIM, 1>(pd, qs, is, cs, ks, lane, idx, found, second);
+            for (int u = 0; u < 2; ++u) {
+                qs[u] = __builtin_amdgcn_readlane(q, src[u]);
+                is[u] = __builtin_amdgcn_readlane(idx1, src[u]);
+                cs[u] = __builtin_amdgcn_readlane(code, src[u]);
+                ks[u] = __builtin_amdgcn_readlane(kind1, src[u]);
+            }
+            if (dir == 0) rescan_groups<DIM, 0>(pd, qs, is, cs, ks, lane, idx, found, second);
+            else rescan_groups<DIM, 1>(pd, qs, is, cs, ks, lane, idx, found, second);
 #pragma unroll
-        for (int u = 0; u < 2; ++u)
-            if (lane == src[u]) { rbest = found[u]; rsecond = second[u]; ridx = idx[u]; }
-    }
-    if (refine) {
-        // the table lookups of all rescanned queries of the wave at once
-        rsecond = max(rsecond, ip2);
-        res = accept_match(rbest, rsecond, ridx, tab);
-        // accepted although two candidates tie for best (0/0 distances): the index the
-        // reference keeps depends on scan order -- leave it to the sequential scan
-        if (res >= 0 && rsecond == rbest) exact = true;
-    }
-    // Ordinary queries whose best candidate is a special descriptor of the other set (rare): the whole
-    // wave scores that set's special descriptors for one query at a time -- eight lanes per candidate,
-    // exact top-2 on keys value * 512 + slot (slots < 512 = special_kernel_max; inner products < 2^22 here:
-    // the wrap-exact path has taken anything above 65535).
-    unsigned long long todo2 = __ballot(sp_scan);
-    while (todo2) {
-        const int src = __ffsll((long long)todo2) - 1;
-        todo2 &= todo2 - 1;
-        const int qs = __builtin_amdgcn_readlane(q, src);
-        int wb, ws, wi;
-        scan_specials<DIM>(pd, dir, qs, lane, wb, ws, wi);
-        if (lane == src) { rbest = wb; rsecond = ws; ridx = wi; }
-    }
-    if (sp_scan) {
-        rsecond = max(max(rsecond, sp_m1), ip2);
-        res = accept_match(rbest, rsecond, ridx, tab);
-        if (res >= 0 && rsecond == rbest) exact = true;
-    }
-    if (exact) {
-        const int slot = atomicAdd(exact_count, 1);
-        if (slot < exact_cap) {
-            ExactItem it;
-            it.problem = problem; it.dir = dir; it.query = q;
-            exact_items[slot] = it;
+            for (int u = 0; u < 2; ++u)
+                if (lane == src[u]) { rbest = found[u]; rsecond = second[u]; ridx = idx[u]; }
         }
+        if (refine) {
+            // the table lookups of all rescanned queries of the wave at once
+            rsecond = max(rsecond, ip2);
+            res = accept_match(rbest, rsecond, ridx, tab);
+            // accepted although two candidates tie for best (0/0 distances): the index the
+            // reference keeps depends on scan order -- leave it to the sequential scan
+            if (res >= 0 && rsecond == rbest) exact = true;
+        }
+        // Ordinary queries whose best candidate is a special descriptor of the other set (rare): the whole
+        // wave scores that set's special descriptors for one query at a time -- eight lanes per candidate,
+        // exact top-2 on keys value * 512 + slot (slots < 512 = special_kernel_max; inner products < 2^22 here:
+        // the wrap-exact path has taken anything above 65535).
+        unsigned long long todo2 = __ballot(sp_scan);
+        while (todo2) {
+            const int src = __ffsll((long long)todo2) - 1;
+            todo2 &= todo2 - 1;
+            const int qs = __builtin_amdgcn_readlane(q, src);
+            int wb, ws, wi;
+            scan_specials<DIM>(pd, dir, qs, lane, wb, ws, wi);
+            if (lane == src) { rbest = wb; rsecond = ws; ridx = wi; }
+        }
+        if (sp_scan) {
+            rsecond = max(max(rsecond, sp_m1), ip2);
+            res = accept_match(rbest, rsecond, ridx, tab);
+            if (res >= 0 && rsecond == rbest) exact = true;
+        }
+        if (exact) {
+            const int slot = atomicAdd(exact_count, 1);
+            if (slot < exact_cap) {
+                ExactItem it;
+                it.problem = problem; it.dir = dir; it.query = q;
+                exact_items[slot] = it;
+            }
+        }
+        if (active && !deferred) out[q] = res;
     }
-    if (active && !deferred) out[q] = res;
 }
 
 void launch_match_finish(const MatchProblem *d_problems, int num_problems, int max_n,
@@ -1254,18 +1278,18 @@ void launch_match_finish(const MatchProblem *d_problems, int num_problems, int m
     ExactItem *exact_items, int32_t *exact_count, int exact_cap, int32_t *rs_count, RescoreItem *rs_items, hipStream_t s)
 {
     if (num_problems <= 0 || max_n <= 0) return;
-    const int blocks_per_dir = (max_n + 127) / 128;
-    const int64_t total = (int64_t)blocks_per_dir * 2 * num_problems;
+    const int spans_per_dir = (max_n + kFinishSpan - 1) / kFinishSpan;
+    const int64_t total = (int64_t)spans_per_dir * 2 * num_problems;
     if (total > INT_MAX) return;    // cannot happen: launches are sized by pairs_per_batch
     const dim3 grid((unsigned)total);
     if (tab.is_signed)
-        hipLaunchKernelGGL((match_finish_kernel<64, true>), grid, dim3(128), 0, s, d_problems, rowparts,
+        hipLaunchKernelGGL((match_finish_kernel<64, true>), grid, dim3(kFinishThreads), 0, s, d_problems, rowparts,
             colparts, sp_parts, sp_col, tab, force_exact, exact_items, exact_count, exact_cap, nullptr, nullptr,
-            blocks_per_dir, (int)total);
+            spans_per_dir, (int)total);
     else
-        hipLaunchKernelGGL((match_finish_kernel<128, false>), grid, dim3(128), 0, s, d_problems, rowparts,
+        hipLaunchKernelGGL((match_finish_kernel<128, false>), grid, dim3(kFinishThreads), 0, s, d_problems, rowparts,
             colparts, sp_parts, sp_col, tab, force_exact, exact_items, exact_count, exact_cap, rs_count, rs_items,
-            blocks_per_dir, (int)total);
+            spans_per_dir, (int)total);
 }
 
 // ---------------------------------------------------------------------------
