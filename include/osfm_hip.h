@@ -46,7 +46,7 @@ OSFM_API const char *osfm_last_error(void);
  * under new symbol names by this header (see below it), and the symbols a caller built against the earlier header
  * binds keep the earlier, shorter layout.  Such a caller still runs correctly, so the version is still 102.  The
  * consensus filter (osfm_ba_consensus, osfm_scene_filter_consensus and their structs) is new entries only, and so
- * is the observation refinement (osfm_refine_* and its structs). */
+ * are the observation refinement (osfm_refine_* and its structs) and the dense plane sweep (osfm_dense_*). */
 #define OSFM_ABI_VERSION 102
 OSFM_API int osfm_version(void);
 /* Number of visible HIP devices (0 when there is none). */
@@ -1599,6 +1599,91 @@ OSFM_API int osfm_refine_set_image_from_front(osfm_refiner *r, int view, osfm_vi
 OSFM_API int osfm_refine_tracks(osfm_refiner *r, int64_t num_tracks, const int64_t *offsets, const int32_t *view, const double *xy,
     const uint8_t *alive, const double *init_affine, const osfm_refine_options *opts, double *out_xy, double *out_affine,
     double *score, int32_t *status, int32_t *iterations, osfm_refine_stats *stats);
+
+/* ---- Dense depth maps by orthographic plane sweep, and their fusion into one point cloud -------------------------
+ * No counterpart in the reference; a caller of it runs the step behind the last adjustment.
+ * tests/dense_restatement.py is the definition, DESIGN.md "Dense plane sweep" describes it.  In short: every view v is
+ * an affine camera, pixel = A_v X + t_v with P_v = [A_v | t_v] ([2][4] doubles, pixel centres at integers as in
+ * osfm_view_front_download's positions).  A reference view r has the viewing axis d_r = (a0 x a1) / |a0 x a1| and
+ * B_r = A_r^T (A_r A_r^T)^-1; its pixel x at depth z is the point X = B_r (x - t_r) + z d_r, seen in a source s at
+ * (A_s B_r) x + (t_s - A_s B_r t_r) + z A_s d_r.  A sweep scores the depths z_k = z_min + k dz, k < num_depths: the
+ * (2 radius + 1)^2 window of reference texels around x against the bilinear samples of the source at the warped
+ * positions of the same pixels, by zero-mean normalised cross-correlation (float32 sums of the grey values minus
+ * 128).  A source counts at a depth when every sample of the window lies in [0, width - 1] x [0, height - 1] and the
+ * samples' variance is at least min_contrast^2; c[k] is the mean score over the sources that count, if there are
+ * min_sources of them.  The best depth is the lowest k of the largest c[k], refined by the parabola through its two
+ * neighbours.  One status per pixel; the first test that fails decides: */
+#define OSFM_DENSE_OK 0
+#define OSFM_DENSE_BORDER 1             /* the window leaves the reference image */
+#define OSFM_DENSE_FLAT 2               /* variance of the reference window below min_contrast^2 */
+#define OSFM_DENSE_NO_SOURCES 3         /* no depth at which min_sources sources count */
+#define OSFM_DENSE_LOW_SCORE 4          /* the best c[k] below min_score */
+#define OSFM_DENSE_RANGE_EDGE 5         /* the best k is 0 or num_depths - 1, or a neighbour of it has no c */
+#define OSFM_DENSE_INCONSISTENT 6       /* osfm_dense_fuse: fewer than min_consistent other views agree */
+#define OSFM_DENSE_DUPLICATE 7          /* osfm_dense_fuse: a view with a smaller index agrees and emits the point */
+#define OSFM_DENSE_NUM_STATUS 8
+
+typedef struct osfm_dense_options {
+    int32_t radius;           /* 3: a 7 x 7 window; 1..7 */
+    int32_t min_sources;      /* 2; 1..8 */
+    int32_t min_consistent;   /* 2; >= 0 */
+    int32_t reserved;
+    double min_contrast;      /* 2.0 grey levels; > 0 */
+    double min_score;         /* 0.8; -1..1 */
+    double consistency_tol;   /* 2.0 depth steps of the supporting view; >= 0 */
+} osfm_dense_options;
+OSFM_API int osfm_dense_options_default(osfm_dense_options *opts);
+/* The shape of the sweep kernel as built: the tile of reference pixels a workgroup owns, and the largest radius,
+ * number of sources per sweep and number of depths it takes.  Any pointer may be NULL. */
+OSFM_API int osfm_dense_limits(int32_t *tile_w, int32_t *tile_h, int32_t *max_radius, int32_t *max_sources, int32_t *max_depths);
+/* Diagnostic of tools/dense_timing.py: the sweeps that follow (of every handle of the process) leave one part of the
+ * kernel's work out, so that its share of the time shows -- 1: the texel gather, 2: the double arithmetic of the warped
+ * positions (float32 instead), 3: all taps of the box sums but one; 0: the kernel as it is.  Their results mean
+ * nothing.  Returns the mode that was set before. */
+OSFM_API int osfm_dense_debug_ablation(int mode);
+
+typedef struct osfm_dense_stats {
+    int64_t status_count[OSFM_DENSE_NUM_STATUS];    /* pixels per status: of the swept view, or after a fusion of all swept views */
+    int64_t samples;                                /* sweep: warped samples taken (halo texels x depths x sources) */
+    double device_ms;                               /* the kernels, by device events */
+} osfm_dense_stats;
+
+typedef struct osfm_dense osfm_dense;
+
+/* The handle holds one grey image per view (float32, as the refiner's), the cameras, and the depth map of every view
+ * swept since the cameras were set: all booked in osfm_library_memory as device_buffer_bytes. */
+OSFM_API int osfm_dense_create(int device, int num_views, osfm_dense **out);
+OSFM_API int osfm_dense_destroy(osfm_dense *d);
+/* The two setters of the refiner (osfm_refine_set_image, osfm_refine_set_image_from_front), same conversion, same
+ * errors.  A new image drops the view's depth map. */
+OSFM_API int osfm_dense_set_image(osfm_dense *d, int view, const uint8_t *pixels, int width, int height, int channels);
+OSFM_API int osfm_dense_set_image_from_front(osfm_dense *d, int view, osfm_view_front *front);
+/* P [num_views][2][4].  Clears all depth maps.  OSFM_E_ARG: a value that is not finite, or an A_v without rank 2. */
+OSFM_API int osfm_dense_set_cameras(osfm_dense *d, const double *P);
+/* The depth map of view ref against sources[num_sources] (1..max_sources other views, none twice).  opts NULL: the
+ * defaults.  Outputs, each [height][width] of the view's image and each may be NULL: depth (NaN where the status is
+ * not OSFM_DENSE_OK), score (c of the best depth; 0 there), status.  The map stays on the device for osfm_dense_fuse.
+ * The result repeats to the bit and does not depend on what else was swept.
+ *   OSFM_E_ARG    null handle or sources, options or num_depths (3..max_depths) out of range, dz <= 0 or values not
+ *                 finite, num_sources outside 1..max_sources or below min_sources, a source equal to ref or repeated
+ *   OSFM_E_RANGE  a view id outside [0, num_views)
+ *   OSFM_E_STATE  no cameras, or ref or a source without an image
+ * None of them writes an output. */
+OSFM_API int osfm_dense_sweep(osfm_dense *d, int ref, int num_sources, const int32_t *sources, double z_min, double dz,
+    int num_depths, const osfm_dense_options *opts, double *depth, float *score, uint8_t *status, osfm_dense_stats *stats);
+/* Consistency and fusion over all views swept since the cameras were set.  An OK pixel of view r with point X looks, in
+ * every other swept view s in ascending order, at the pixel nearest to A_s X + t_s: s supports it when that pixel is
+ * inside and OK and its depth differs from d_s . X by at most consistency_tol steps of s.  Fewer than min_consistent
+ * supporters: INCONSISTENT; else a supporter with a smaller index: DUPLICATE.  The cloud is what stays OK, in (view,
+ * row, column) order; *num_points (may be NULL) is its size.  The sweeps' own results are not changed. */
+OSFM_API int osfm_dense_fuse(osfm_dense *d, const osfm_dense_options *opts, int64_t *num_points, osfm_dense_stats *stats);
+/* The status of a swept view after the last fusion, [height][width].  OSFM_E_STATE without one. */
+OSFM_API int osfm_dense_download_status(osfm_dense *d, int view, uint8_t *status);
+/* The cloud of the last fusion: points [N][3], view [N], pixel [N][2] (x, y); each may be NULL.  OSFM_E_STATE without a
+ * fusion, OSFM_E_CAPACITY when capacity < N. */
+OSFM_API int osfm_dense_download_cloud(osfm_dense *d, int64_t capacity, double *points, int32_t *view, int32_t *pixel);
+/* Binary little-endian PLY: float x, y, z and uchar red, green, blue per vertex.  rgb [n][3] (NULL: zeros). */
+OSFM_API int osfm_dense_cloud_write(const char *path, int64_t n, const double *points, const uint8_t *rgb);
 
 #ifdef __cplusplus
 }

@@ -346,6 +346,25 @@ class RefineStats(C.Structure):
         return d
 
 
+class DenseOptions(C.Structure):
+    """osfm_dense_options."""
+    _fields_ = [(n, C.c_int32) for n in ("radius", "min_sources", "min_consistent", "reserved")] + \
+               [(n, C.c_double) for n in ("min_contrast", "min_score", "consistency_tol")]
+
+
+DENSE_STATUS = ("ok", "border", "flat", "no_sources", "low_score", "range_edge", "inconsistent", "duplicate")
+(DENSE_OK, DENSE_BORDER, DENSE_FLAT, DENSE_NO_SOURCES, DENSE_LOW_SCORE, DENSE_RANGE_EDGE, DENSE_INCONSISTENT,
+ DENSE_DUPLICATE) = range(8)
+
+
+class DenseStats(C.Structure):
+    """osfm_dense_stats."""
+    _fields_ = [("status_count", C.c_int64 * len(DENSE_STATUS)), ("samples", C.c_int64), ("device_ms", C.c_double)]
+
+    def counters(self) -> dict:
+        return {n: int(self.status_count[i]) for i, n in enumerate(DENSE_STATUS)}
+
+
 # every symbol include/osfm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "osfm_last_error", "osfm_version", "osfm_device_count", "osfm_device_memory", "osfm_library_memory", "osfm_trim_device_memory", "osfm_ransac_selfcheck", "osfm_ba_debug_chol_trace", "osfm_ba_debug_flow_spin_limit", "osfm_ba_debug_order",
@@ -384,6 +403,9 @@ EXPORTS = [
     "osfm_tracks_filter_marked",
     "osfm_refine_options_default", "osfm_refine_create", "osfm_refine_destroy", "osfm_refine_set_image",
     "osfm_refine_set_image_from_front", "osfm_refine_tracks",
+    "osfm_dense_options_default", "osfm_dense_limits", "osfm_dense_debug_ablation", "osfm_dense_create", "osfm_dense_destroy", "osfm_dense_set_image",
+    "osfm_dense_set_image_from_front", "osfm_dense_set_cameras", "osfm_dense_sweep", "osfm_dense_fuse",
+    "osfm_dense_download_status", "osfm_dense_download_cloud", "osfm_dense_cloud_write",
 ]
 
 # osfm_track_feature as a numpy record (32 bytes, no padding)
@@ -462,6 +484,20 @@ lib.osfm_refine_set_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, 
 lib.osfm_refine_set_image_from_front.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
 lib.osfm_refine_tracks.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(RefineOptions)] + [C.c_void_p] * 5 + \
                                   [C.POINTER(RefineStats)]
+lib.osfm_dense_options_default.argtypes = [C.POINTER(DenseOptions)]
+lib.osfm_dense_limits.argtypes = [C.POINTER(C.c_int32)] * 5
+lib.osfm_dense_debug_ablation.argtypes = [C.c_int]
+lib.osfm_dense_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+lib.osfm_dense_destroy.argtypes = [C.c_void_p]
+lib.osfm_dense_set_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
+lib.osfm_dense_set_image_from_front.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+lib.osfm_dense_set_cameras.argtypes = [C.c_void_p, C.c_void_p]
+lib.osfm_dense_sweep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int, C.POINTER(DenseOptions),
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenseStats)]
+lib.osfm_dense_fuse.argtypes = [C.c_void_p, C.POINTER(DenseOptions), C.POINTER(C.c_int64), C.POINTER(DenseStats)]
+lib.osfm_dense_download_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+lib.osfm_dense_download_cloud.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.osfm_dense_cloud_write.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p]
 lib.osfm_ba_debug_cholesky_solve.restype = C.c_int
 lib.osfm_ba_debug_cholesky_solve.argtypes = [C.c_int, C.c_int, _f64p, _f64p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, _f64p, _i32p, _i32p]
@@ -585,6 +621,24 @@ def default_refine_options(**kw) -> RefineOptions:
             raise TypeError(f"osfm_refine_options has no field {k!r}")
         setattr(o, k, v)
     return o
+
+
+def default_dense_options(**kw) -> DenseOptions:
+    """osfm_dense_options_default with the given fields replaced."""
+    o = DenseOptions()
+    check(lib.osfm_dense_options_default(C.byref(o)))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"osfm_dense_options has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def dense_limits():
+    """(tile_w, tile_h, max_radius, max_sources, max_depths) of the plane-sweep kernel."""
+    v = [C.c_int32() for _ in range(5)]
+    check(lib.osfm_dense_limits(*[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
 
 
 def default_sift_options() -> SiftOptions:

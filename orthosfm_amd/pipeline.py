@@ -1357,13 +1357,67 @@ def camera_to_world_matrices(model, cam_params):
     return out
 
 
-def save_project(res: Result, model, folder, image_names=None, feature_rgb=None):
+@dataclass
+class DenseResult:
+    points: np.ndarray        # float64 [N, 3]
+    rgb: np.ndarray           # uint8 [N, 3]: the pixel of the emitting view (a grey image gives r = g = b)
+    view: np.ndarray          # int32 [N]
+    pixel: np.ndarray         # int32 [N, 2]
+    plans: list               # per view: dense.ViewPlan, or None for a view that was not swept
+    maps: list                # per view: dense.DepthMap (keep_maps=True), else None
+    counters: dict            # pixels per status after the fusion
+    sweep_ms: float           # device time of all sweeps
+    fuse_ms: float
+
+
+def densify(images, model, cam_params, points, visibility, device=0, views=None, keep_maps=False, max_sources=4, **options):
+    """A dense point cloud from adjusted cameras: every view in `views` (None: all) is swept against the sources
+    dense.plan_view picks among them, over the depth range of its own sparse points, then all maps are fused.
+    images: uint8 [h, w] or [h, w, 3] per view; cam_params [V, 7]; points [M, 3+]; visibility: per view the indices
+    of the sparse points it sees (what the depth range is taken from).  options: fields of osfm_dense_options.
+    This step has no counterpart in the reference."""
+    from . import dense
+    V = len(images)
+    views = list(range(V)) if views is None else [int(v) for v in views]
+    heights = [np.asarray(im).shape[0] for im in images]
+    widths = [np.asarray(im).shape[1] for im in images]
+    P = dense.affine_cameras(model, np.asarray(cam_params, dtype=np.float64)[:V], widths, heights)
+    pts = np.asarray(points, dtype=np.float64)[:, :3]
+    plans, maps = [None] * V, [None] * V
+    sweep_ms = 0.0
+    with dense.DenseStereo(device, V) as ds:
+        for v in views:
+            ds.set_image(v, images[v])
+        ds.set_cameras(P)
+        for v in views:
+            plan = dense.plan_view(P, v, pts[np.asarray(visibility[v], dtype=np.int64)], views, max_sources=max_sources)
+            if plan is None or len(plan.sources) < int(options.get("min_sources", 2)):
+                continue
+            plans[v] = plan
+            m = ds.sweep(v, plan.sources, plan.z_min, plan.dz, plan.num_depths, download=keep_maps, **options)
+            sweep_ms += m.stats.device_ms
+            if keep_maps:
+                maps[v] = m
+        cloud = ds.fuse(**options)
+    rgb = np.zeros((cloud.points.shape[0], 3), np.uint8)
+    for v in views:
+        sel = cloud.view == v
+        if sel.any():
+            im = np.asarray(images[v])
+            px = im[cloud.pixel[sel, 1], cloud.pixel[sel, 0]]
+            rgb[sel] = px[:, None] if im.ndim == 2 else px[:, :3]
+    return DenseResult(cloud.points, rgb, cloud.view, cloud.pixel, plans, maps, cloud.stats.counters(), sweep_ms,
+                       cloud.stats.device_ms)
+
+
+def save_project(res: Result, model, folder, image_names=None, feature_rgb=None, dense_cloud=None):
     """The files orthosfm::reconstruct leaves in the project folder (reconstruct.cpp:125,
     :160, :168, :290), written through the C ABI of the text formats: tracks.txt (all
     tracks, as built), cameras.txt (aligned cameras), sparse_cloud.ply (surviving tracks
     with a point), time_measurements.txt.  feature_rgb: uint8 [num_features, 3] in the
     table's feature order (tracks_from_images' info["feature_rgb"]), the colours that
-    propagateColorsToTracks gives the features before the reference writes them; None: zeros."""
+    propagateColorsToTracks gives the features before the reference writes them; None: zeros.
+    dense_cloud: a DenseResult of densify(), written as dense_cloud.ply (binary); None: no such file."""
     from . import formats as F
     os.makedirs(folder, exist_ok=True)
     tt = res.tracks
@@ -1388,3 +1442,6 @@ def save_project(res: Result, model, folder, image_names=None, feature_rgb=None)
     tm = res.timings
     F.save_runtimes_to_txt_native(os.path.join(folder, "time_measurements.txt"), tm.upload_s,
                                   tm.matching_s + tm.tracks_s + tm.convert_s, tm.groups_s + tm.pose_s, tm.total_s)
+    if dense_cloud is not None:
+        from .dense import write_cloud
+        write_cloud(os.path.join(folder, "dense_cloud.ply"), dense_cloud.points, dense_cloud.rgb)
