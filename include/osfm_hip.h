@@ -46,7 +46,8 @@ OSFM_API const char *osfm_last_error(void);
  * under new symbol names by this header (see below it), and the symbols a caller built against the earlier header
  * binds keep the earlier, shorter layout.  Such a caller still runs correctly, so the version is still 102.  The
  * consensus filter (osfm_ba_consensus, osfm_scene_filter_consensus and their structs) is new entries only, and so
- * are the observation refinement (osfm_refine_* and its structs) and the dense plane sweep (osfm_dense_*). */
+ * are the observation refinement (osfm_refine_* and its structs), the dense plane sweep (osfm_dense_*) and the
+ * depth-map meshes (osfm_dense_set_map, osfm_dense_mesh_*, osfm_dense_download_mesh and their structs). */
 #define OSFM_ABI_VERSION 102
 OSFM_API int osfm_version(void);
 /* Number of visible HIP devices (0 when there is none). */
@@ -1684,6 +1685,74 @@ OSFM_API int osfm_dense_download_status(osfm_dense *d, int view, uint8_t *status
 OSFM_API int osfm_dense_download_cloud(osfm_dense *d, int64_t capacity, double *points, int32_t *view, int32_t *pixel);
 /* Binary little-endian PLY: float x, y, z and uchar red, green, blue per vertex.  rgb [n][3] (NULL: zeros). */
 OSFM_API int osfm_dense_cloud_write(const char *path, int64_t n, const double *points, const uint8_t *rgb);
+
+/* ---- A mesh per depth map: islands, triangles, normals, scales, confidences ---------------------------------------
+ * What MVE does between dmrecon and fssrecon (depthmap_cleanup, depthmap_triangulate, the vertex normals,
+ * depthmap_mesh_confidences, the scale of scene2pset), on the image grid of an orthographic view; tests/mesh_restatement.py
+ * is the definition, DESIGN.md "Depth-map meshes" describes it.  The footprint of a view is f = sqrt(|b0 x b1|) with b0,
+ * b1 the columns of B: the side of a world square with a pixel's area.
+ *
+ * osfm_dense_set_map uploads a depth map in the layout osfm_dense_sweep returns ([height][width] each; score NULL:
+ * zeros): the view then counts as swept -- an earlier fusion is gone, as after a sweep of it.
+ *   OSFM_E_ARG    null handle, depth or status; a status above OSFM_DENSE_RANGE_EDGE; a depth that is not finite where
+ *                 the status is OSFM_DENSE_OK; dz not finite or <= 0
+ *   OSFM_E_RANGE  view outside [0, num_views)
+ *   OSFM_E_STATE  no cameras, or the view has no image (which fixes the size)
+ * None of them changes anything. */
+OSFM_API int osfm_dense_set_map(osfm_dense *d, int view, const double *depth, const float *score, const uint8_t *status, double dz);
+
+#define OSFM_MESH_VERTEX_SIMPLE 0       /* the incident triangles chain into a closed fan */
+#define OSFM_MESH_VERTEX_BORDER 1       /* one open chain */
+#define OSFM_MESH_VERTEX_COMPLEX 2      /* more than one chain */
+
+typedef struct osfm_dense_mesh_options {
+    double dd_factor;                   /* 5.0: an edge longer in depth than dd_factor footprints (sqrt 2 times that on a
+                                         * diagonal) is a discontinuity and drops its triangles; 0: none is; >= 0 */
+    int32_t confidence_iterations;      /* 3: confidence min(distance to the mesh border, K) / K; 0: all 1; 0..max */
+    int32_t min_island;                 /* 0: 4-connected components of fewer solid pixels are cleared; >= 0 */
+    int32_t use_fused;                  /* 0; 1: a pixel is solid only if the last fusion left it OK or DUPLICATE */
+    int32_t reserved;
+} osfm_dense_mesh_options;
+OSFM_API int osfm_dense_mesh_options_default(osfm_dense_mesh_options *opts);
+/* The shape of the kernels as built: the tile of the component labelling, the largest confidence_iterations.  Any
+ * pointer may be NULL. */
+OSFM_API int osfm_dense_mesh_limits(int32_t *label_tile_w, int32_t *label_tile_h, int32_t *max_confidence_iterations);
+
+#define OSFM_MESH_NUM_STAGES 5          /* labelling, triangles, vertices, confidence, scans and emission */
+typedef struct osfm_dense_mesh_stats {
+    int64_t pixels_solid;               /* before the islands are cleared */
+    int64_t pixels_island;              /* cleared as islands */
+    int64_t components;                 /* 4-connected components of the solid pixels (0 with min_island 0: no labelling) */
+    int64_t triangles_dropped;          /* candidate triangles with a discontinuity on an edge */
+    int64_t vertices_simple, vertices_border, vertices_complex;
+    double threshold_steps;             /* dd_factor f / dz: the straight-edge threshold in depth steps of the view */
+    double device_ms;                   /* all kernels, by device events */
+    double stage_ms[OSFM_MESH_NUM_STAGES];
+} osfm_dense_mesh_stats;
+
+/* The mesh of one view's depth map (opts NULL: the defaults); it stays on the device until the next call, or until the
+ * cameras, the view's image or the view's map change.  Solid pixels are those with sweep status OSFM_DENSE_OK (and see
+ * use_fused); every 2 x 2 block of pixels gives up to two triangles in MVE's vertex order, blocks row-major; vertices
+ * are the pixels a triangle names, row-major.  Repeats to the bit.  num_vertices, num_triangles, stats may be NULL.
+ *   OSFM_E_ARG      null handle; dd_factor negative or not finite, confidence_iterations outside 0..max, min_island < 0
+ *   OSFM_E_RANGE    view outside [0, num_views)
+ *   OSFM_E_STATE    the view has no depth map; use_fused without a fusion
+ *   OSFM_E_NUMERIC  the labelling ran into its iteration bound (65536 steps of one walk: a defect, or a component that
+ *                   winds through more tile-local pieces than that in one chain; reported instead of a hang): no mesh
+ * None of them writes an output. */
+OSFM_API int osfm_dense_mesh_view(osfm_dense *d, int view, const osfm_dense_mesh_options *opts, int64_t *num_vertices,
+    int64_t *num_triangles, osfm_dense_mesh_stats *stats);
+/* The mesh of the last osfm_dense_mesh_view: points [V][3], unit normals [V][3] (towards the camera), confidence [V],
+ * scale [V] (mean length of the mesh edges at the vertex), pixel [V][2] (x, y), vclass [V] (OSFM_MESH_VERTEX_*),
+ * triangles [T][3] (vertex indices); each may be NULL.  OSFM_E_STATE without a mesh, OSFM_E_CAPACITY when
+ * capacity_vertices < V or capacity_triangles < T. */
+OSFM_API int osfm_dense_download_mesh(osfm_dense *d, int64_t capacity_vertices, int64_t capacity_triangles, double *points,
+    double *normals, float *confidence, double *scale, int32_t *pixel, uint8_t *vclass, int32_t *triangles);
+/* Binary little-endian PLY with MVE's property names: float x, y, z, nx, ny, nz, uchar red, green, blue, float
+ * confidence, value (the scale) per vertex; faces as "list uchar int vertex_indices", left out with num_triangles 0
+ * (a point set, as fssrecon reads it).  NULL: normals zeros, rgb zeros, confidence ones, scale zeros. */
+OSFM_API int osfm_dense_mesh_write(const char *path, int64_t num_vertices, const double *points, const double *normals,
+    const uint8_t *rgb, const float *confidence, const double *scale, int64_t num_triangles, const int32_t *triangles);
 
 #ifdef __cplusplus
 }

@@ -365,6 +365,25 @@ class DenseStats(C.Structure):
         return {n: int(self.status_count[i]) for i, n in enumerate(DENSE_STATUS)}
 
 
+class DenseMeshOptions(C.Structure):
+    """osfm_dense_mesh_options."""
+    _fields_ = [("dd_factor", C.c_double)] + [(n, C.c_int32) for n in ("confidence_iterations", "min_island", "use_fused", "reserved")]
+
+
+MESH_VERTEX_SIMPLE, MESH_VERTEX_BORDER, MESH_VERTEX_COMPLEX = range(3)
+MESH_STAGES = ("label", "triangles", "vertices", "confidence", "emit")
+
+
+class DenseMeshStats(C.Structure):
+    """osfm_dense_mesh_stats."""
+    _fields_ = [(n, C.c_int64) for n in ("pixels_solid", "pixels_island", "components", "triangles_dropped", "vertices_simple",
+                                         "vertices_border", "vertices_complex")] + \
+               [("threshold_steps", C.c_double), ("device_ms", C.c_double), ("stage_ms", C.c_double * len(MESH_STAGES))]
+
+    def counters(self) -> dict:
+        return {n: int(getattr(self, n)) for n, t in self._fields_ if t is C.c_int64}
+
+
 # every symbol include/osfm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "osfm_last_error", "osfm_version", "osfm_device_count", "osfm_device_memory", "osfm_library_memory", "osfm_trim_device_memory", "osfm_ransac_selfcheck", "osfm_ba_debug_chol_trace", "osfm_ba_debug_flow_spin_limit", "osfm_ba_debug_order",
@@ -406,6 +425,8 @@ EXPORTS = [
     "osfm_dense_options_default", "osfm_dense_limits", "osfm_dense_debug_ablation", "osfm_dense_create", "osfm_dense_destroy", "osfm_dense_set_image",
     "osfm_dense_set_image_from_front", "osfm_dense_set_cameras", "osfm_dense_sweep", "osfm_dense_fuse",
     "osfm_dense_download_status", "osfm_dense_download_cloud", "osfm_dense_cloud_write",
+    "osfm_dense_set_map", "osfm_dense_mesh_options_default", "osfm_dense_mesh_limits", "osfm_dense_mesh_view",
+    "osfm_dense_download_mesh", "osfm_dense_mesh_write",
 ]
 
 # osfm_track_feature as a numpy record (32 bytes, no padding)
@@ -498,6 +519,14 @@ lib.osfm_dense_fuse.argtypes = [C.c_void_p, C.POINTER(DenseOptions), C.POINTER(C
 lib.osfm_dense_download_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
 lib.osfm_dense_download_cloud.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.osfm_dense_cloud_write.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p]
+lib.osfm_dense_set_map.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double]
+lib.osfm_dense_mesh_options_default.argtypes = [C.POINTER(DenseMeshOptions)]
+lib.osfm_dense_mesh_limits.argtypes = [C.POINTER(C.c_int32)] * 3
+lib.osfm_dense_mesh_view.argtypes = [C.c_void_p, C.c_int, C.POINTER(DenseMeshOptions), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                     C.POINTER(DenseMeshStats)]
+lib.osfm_dense_download_mesh.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 7
+lib.osfm_dense_mesh_write.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                      C.c_void_p]
 lib.osfm_ba_debug_cholesky_solve.restype = C.c_int
 lib.osfm_ba_debug_cholesky_solve.argtypes = [C.c_int, C.c_int, _f64p, _f64p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, _f64p, _i32p, _i32p]
@@ -632,6 +661,24 @@ def default_dense_options(**kw) -> DenseOptions:
             raise TypeError(f"osfm_dense_options has no field {k!r}")
         setattr(o, k, v)
     return o
+
+
+def default_dense_mesh_options(**kw) -> DenseMeshOptions:
+    """osfm_dense_mesh_options_default with the given fields replaced."""
+    o = DenseMeshOptions()
+    check(lib.osfm_dense_mesh_options_default(C.byref(o)))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"osfm_dense_mesh_options has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def dense_mesh_limits():
+    """(label_tile_w, label_tile_h, max_confidence_iterations) of the mesh kernels."""
+    v = [C.c_int32() for _ in range(3)]
+    check(lib.osfm_dense_mesh_limits(*[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
 
 
 def dense_limits():

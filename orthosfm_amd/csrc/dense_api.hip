@@ -8,26 +8,11 @@
 
 #include <hipcub/hipcub.hpp>
 
-#include "dense_kernels.h"
-#include "refine_kernels.h"
+#include "dense_handle.h"
 #include "view_front.h"
 
 using namespace osfm;
-
-struct osfm_dense {
-    int device = 0, num_views = 0;
-    hipStream_t stream = nullptr;                  // image uploads and conversions
-    std::vector<DeviceBuffer> grey;                // float32 [h][w] per view
-    std::vector<refine::Image> images;
-    std::vector<DeviceBuffer> depth, score, status, final_status;      // per swept view
-    std::vector<dense::ViewGeo> geo;
-    std::vector<uint8_t> swept;
-    std::vector<double> dz;
-    bool cameras = false, fused = false;
-    int64_t cloud_size = 0;
-    DeviceBuffer staging, table, flags, scan, scan_temp, cloud_points, cloud_view, cloud_pixel;
-    ~osfm_dense() { stream_destroy(stream); }
-};
+using osfm::dense::drop_map;
 
 namespace {
 
@@ -62,13 +47,6 @@ int check_options(const char *api, const osfm_dense_options &o)
         return OSFM_E_ARG;
     }
     return OSFM_OK;
-}
-
-// a new image or new cameras: what was swept with the old ones is gone
-void drop_map(osfm_dense *d, int view)
-{
-    d->swept[view] = 0;
-    d->fused = false;
 }
 
 void count_status(const std::vector<uint8_t> &st, osfm_dense_stats *stats)

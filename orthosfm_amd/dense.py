@@ -109,6 +109,21 @@ class Cloud:
     stats: capi.DenseStats
 
 
+@dataclass
+class ViewMesh:
+    """The mesh of one view's depth map (osfm_dense_mesh_view)."""
+    view: int
+    points: np.ndarray        # float64 [V, 3]
+    normals: np.ndarray       # float64 [V, 3]: unit, towards the camera; 0 where the incident faces cancel
+    confidence: np.ndarray    # float32 [V]: 0 on the border of the mesh, 1 from confidence_iterations edges inside
+    scale: np.ndarray         # float64 [V]: mean length of the mesh edges at the vertex
+    pixel: np.ndarray         # int32 [V, 2]: x, y in the view's image
+    vclass: np.ndarray        # uint8 [V]: capi.MESH_VERTEX_*
+    triangles: np.ndarray     # int32 [T, 3]: vertex indices, in MVE's winding
+    stats: capi.DenseMeshStats
+    rgb: np.ndarray = None    # uint8 [V, 3]: the vertices' pixels, where a caller has the image (pipeline.densify)
+
+
 class DenseStereo(_Handle):
     """One osfm_dense: a grey image per view on the device, the cameras, and the depth maps swept so far."""
     _prefix = "dense"
@@ -168,6 +183,77 @@ class DenseStereo(_Handle):
         out = np.zeros(shape if shape is not None else (1, 1), np.uint8)
         capi.check(capi.lib.osfm_dense_download_status(self._h, int(view), out.ctypes.data))
         return out
+
+
+    def set_map(self, view: int, depth, status, dz: float, score=None):
+        """osfm_dense_set_map: a depth map from elsewhere, in the layout sweep() returns; the view counts as swept."""
+        shape = self._shape[int(view)] if 0 <= int(view) < self.num_views else None
+        depth = np.ascontiguousarray(depth, dtype=np.float64)
+        status = np.ascontiguousarray(status, dtype=np.uint8)
+        if score is not None:
+            score = np.ascontiguousarray(score, dtype=np.float32)
+        for name, a in (("depth", depth), ("status", status), ("score", score)):
+            if shape is not None and a is not None and a.shape != shape:
+                raise ValueError(f"DenseStereo.set_map: {name} {a.shape}, the view's image is {shape}")
+        capi.check(capi.lib.osfm_dense_set_map(self._h, int(view), depth.ctypes.data, score.ctypes.data if score is not None else None,
+                                               status.ctypes.data, float(dz)))
+
+    def mesh(self, view: int, **options) -> ViewMesh:
+        """osfm_dense_mesh_view and osfm_dense_download_mesh; options: the fields of osfm_dense_mesh_options."""
+        o = capi.default_dense_mesh_options(**options)
+        nv, nt, stats = C.c_int64(), C.c_int64(), capi.DenseMeshStats()
+        capi.check(capi.lib.osfm_dense_mesh_view(self._h, int(view), C.byref(o), C.byref(nv), C.byref(nt), C.byref(stats)))
+        V, T = int(nv.value), int(nt.value)
+        m = ViewMesh(int(view), np.zeros((V, 3)), np.zeros((V, 3)), np.zeros(V, np.float32), np.zeros(V), np.zeros((V, 2), np.int32),
+                     np.zeros(V, np.uint8), np.zeros((T, 3), np.int32), stats)
+        capi.check(capi.lib.osfm_dense_download_mesh(self._h, V, T, m.points.ctypes.data, m.normals.ctypes.data, m.confidence.ctypes.data,
+                                                     m.scale.ctypes.data, m.pixel.ctypes.data, m.vclass.ctypes.data, m.triangles.ctypes.data))
+        return m
+
+
+def write_mesh(path, points, normals=None, rgb=None, confidence=None, scale=None, triangles=None):
+    """osfm_dense_mesh_write: a binary little-endian PLY with MVE's property names (x y z nx ny nz, red green blue,
+    confidence, value); without triangles a point set, as fssrecon reads it."""
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    V = points.shape[0]
+
+    def arg(name, a, dtype, shape):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dtype).reshape(shape)
+        if a.shape[0] != V:
+            raise ValueError(f"write_mesh: {V} points, {a.shape[0]} rows of {name}")
+        return a
+    normals, rgb = arg("normals", normals, np.float64, (-1, 3)), arg("rgb", rgb, np.uint8, (-1, 3))
+    confidence, scale = arg("confidence", confidence, np.float32, (-1,)), arg("scale", scale, np.float64, (-1,))
+    tris = np.ascontiguousarray(triangles if triangles is not None else np.zeros((0, 3)), dtype=np.int32).reshape(-1, 3)
+    p = lambda a: a.ctypes.data if a is not None else None
+    capi.check(capi.lib.osfm_dense_mesh_write(os.fsencode(path), V, points.ctypes.data, p(normals), p(rgb), p(confidence), p(scale),
+                                              tris.shape[0], tris.ctypes.data))
+
+
+def read_mesh(path):
+    """dict of points, normals (float32 [V, 3]), rgb (uint8 [V, 3]), confidence, scale (float32 [V]) and triangles
+    (int32 [T, 3]) of a file write_mesh wrote."""
+    with open(path, "rb") as f:
+        counts = {}
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"read_mesh: {path}: no end_header")
+            if line.startswith(b"element "):
+                counts[line.split()[1].decode()] = int(line.split()[2])
+            if line.strip() == b"end_header":
+                break
+        vrec = np.dtype([("xyz", "<f4", 3), ("n", "<f4", 3), ("rgb", "u1", 3), ("confidence", "<f4"), ("value", "<f4")])
+        frec = np.dtype([("n", "u1"), ("v", "<i4", 3)])
+        V, T = counts.get("vertex", 0), counts.get("face", 0)
+        v = np.frombuffer(f.read(V * vrec.itemsize), dtype=vrec, count=V)
+        t = np.frombuffer(f.read(T * frec.itemsize), dtype=frec, count=T)
+    if T and not (t["n"] == 3).all():
+        raise ValueError(f"read_mesh: {path}: a face that is no triangle")
+    return dict(points=v["xyz"].copy(), normals=v["n"].copy(), rgb=v["rgb"].copy(), confidence=v["confidence"].copy(),
+                scale=v["value"].copy(), triangles=t["v"].copy().reshape(-1, 3))
 
 
 def write_cloud(path, points, rgb=None):

@@ -1368,13 +1368,37 @@ class DenseResult:
     counters: dict            # pixels per status after the fusion
     sweep_ms: float           # device time of all sweeps
     fuse_ms: float
+    meshes: list = None       # densify(meshes=True): per view a dense.ViewMesh, or None for a view that was not swept
+    pset: "PointSet" = None   # densify(meshes=True): the vertices of all meshes with confidence > 0
+    mesh_ms: float = 0.0
 
 
-def densify(images, model, cam_params, points, visibility, device=0, views=None, keep_maps=False, max_sources=4, **options):
+@dataclass
+class PointSet:
+    """An oriented, scaled, confidence-weighted point set: what a surface tool (fssrecon, screened Poisson) reads."""
+    points: np.ndarray        # float64 [N, 3]
+    normals: np.ndarray       # float64 [N, 3]
+    rgb: np.ndarray           # uint8 [N, 3]
+    confidence: np.ndarray    # float32 [N]: in (0, 1]
+    scale: np.ndarray         # float64 [N]
+    view: np.ndarray          # int32 [N]
+    pixel: np.ndarray         # int32 [N, 2]
+
+
+def _pixel_colours(image, pixel):
+    im = np.asarray(image)
+    px = im[pixel[:, 1], pixel[:, 0]]
+    return np.repeat(px[:, None], 3, axis=1).astype(np.uint8) if im.ndim == 2 else px[:, :3].astype(np.uint8)
+
+
+def densify(images, model, cam_params, points, visibility, device=0, views=None, keep_maps=False, max_sources=4, meshes=False,
+            mesh_options=None, **options):
     """A dense point cloud from adjusted cameras: every view in `views` (None: all) is swept against the sources
     dense.plan_view picks among them, over the depth range of its own sparse points, then all maps are fused.
     images: uint8 [h, w] or [h, w, 3] per view; cam_params [V, 7]; points [M, 3+]; visibility: per view the indices
     of the sparse points it sees (what the depth range is taken from).  options: fields of osfm_dense_options.
+    meshes=True: every swept view is also meshed after the fusion (use_fused = 1; mesh_options: further fields of
+    osfm_dense_mesh_options), and the result carries the meshes and their point set.
     This step has no counterpart in the reference."""
     from . import dense
     V = len(images)
@@ -1399,6 +1423,13 @@ def densify(images, model, cam_params, points, visibility, device=0, views=None,
             if keep_maps:
                 maps[v] = m
         cloud = ds.fuse(**options)
+        view_meshes = None
+        if meshes:
+            mo = dict(mesh_options or {}, use_fused=1)
+            view_meshes = [ds.mesh(v, **mo) if plans[v] is not None else None for v in range(V)]
+            for m in view_meshes:
+                if m is not None:
+                    m.rgb = _pixel_colours(images[m.view], m.pixel)
     rgb = np.zeros((cloud.points.shape[0], 3), np.uint8)
     for v in views:
         sel = cloud.view == v
@@ -1406,8 +1437,19 @@ def densify(images, model, cam_params, points, visibility, device=0, views=None,
             im = np.asarray(images[v])
             px = im[cloud.pixel[sel, 1], cloud.pixel[sel, 0]]
             rgb[sel] = px[:, None] if im.ndim == 2 else px[:, :3]
-    return DenseResult(cloud.points, rgb, cloud.view, cloud.pixel, plans, maps, cloud.stats.counters(), sweep_ms,
-                       cloud.stats.device_ms)
+    res = DenseResult(cloud.points, rgb, cloud.view, cloud.pixel, plans, maps, cloud.stats.counters(), sweep_ms,
+                      cloud.stats.device_ms)
+    if meshes:
+        parts = [(m, m.confidence > 0.0) for m in view_meshes if m is not None]
+        cat = lambda pick, shape, dt: np.concatenate([pick(m, k) for m, k in parts]) if parts else np.zeros(shape, dt)
+        res.meshes = view_meshes
+        res.pset = PointSet(cat(lambda m, k: m.points[k], (0, 3), np.float64), cat(lambda m, k: m.normals[k], (0, 3), np.float64),
+                            cat(lambda m, k: m.rgb[k], (0, 3), np.uint8),
+                            cat(lambda m, k: m.confidence[k], (0,), np.float32), cat(lambda m, k: m.scale[k], (0,), np.float64),
+                            cat(lambda m, k: np.full(int(k.sum()), m.view, np.int32), (0,), np.int32),
+                            cat(lambda m, k: m.pixel[k], (0, 2), np.int32))
+        res.mesh_ms = float(sum(m.stats.device_ms for m, _ in parts))
+    return res
 
 
 def save_project(res: Result, model, folder, image_names=None, feature_rgb=None, dense_cloud=None):
@@ -1417,7 +1459,9 @@ def save_project(res: Result, model, folder, image_names=None, feature_rgb=None,
     with a point), time_measurements.txt.  feature_rgb: uint8 [num_features, 3] in the
     table's feature order (tracks_from_images' info["feature_rgb"]), the colours that
     propagateColorsToTracks gives the features before the reference writes them; None: zeros.
-    dense_cloud: a DenseResult of densify(), written as dense_cloud.ply (binary); None: no such file."""
+    dense_cloud: a DenseResult of densify(), written as dense_cloud.ply (binary); None: no such file.  One of
+    densify(meshes=True) also gives dense_pset.ply (points with normals, confidence and scale under MVE's property
+    names) and a dense_mesh_%04d.ply per meshed view."""
     from . import formats as F
     os.makedirs(folder, exist_ok=True)
     tt = res.tracks
@@ -1445,3 +1489,12 @@ def save_project(res: Result, model, folder, image_names=None, feature_rgb=None,
     if dense_cloud is not None:
         from .dense import write_cloud
         write_cloud(os.path.join(folder, "dense_cloud.ply"), dense_cloud.points, dense_cloud.rgb)
+        if dense_cloud.pset is not None:
+            from .dense import write_mesh
+            ps = dense_cloud.pset
+            write_mesh(os.path.join(folder, "dense_pset.ply"), ps.points, ps.normals, ps.rgb, ps.confidence, ps.scale)
+            for m in dense_cloud.meshes:
+                if m is None:
+                    continue
+                write_mesh(os.path.join(folder, "dense_mesh_%04d.ply" % m.view), m.points, m.normals, m.rgb, m.confidence, m.scale,
+                           m.triangles)
