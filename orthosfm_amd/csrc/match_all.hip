@@ -32,32 +32,38 @@ struct ChunkLists {
 };
 
 // The kept pairs' mutual matches of a chunk of n pairs, as chunk_corr (id 1, id 2) records back to back on the
-// device; without verification they go on to corr + 2 * written on the copy stream.
-int compact_chunk(osfm_matcher *m, const ChunkLists &h, int n, int64_t chunk_corr, int32_t *corr, int64_t written, int *chunk_no)
+// device; without verification they go on to corr + 2 * written on the copy stream.  cs: the stream the compaction
+// runs on -- the main stream, or the copy stream itself for a slice whose counts the host has waited for.
+int compact_chunk(osfm_matcher *m, const ChunkLists &h, int n, int64_t chunk_corr, int32_t *corr, int64_t written, int *chunk_no,
+    hipStream_t cs)
 {
     const osfm_match_options &o = m->opts;
-    hipStream_t s = m->stream;
-    OSFM_RETURN_IF(m->d_m12_off.reserve(n * 8));
-    OSFM_RETURN_IF(m->d_corr_off.reserve(n * 8));
-    OSFM_RETURN_IF(m->d_len12.reserve(n * 4));
-    OSFM_RETURN_IF(m->d_keep_pair.reserve(n));
     // without verification two list buffers alternate: the copy of the one is in flight on the
     // copy stream while the next chunk is matched and compacted into the other
     const int cb = o.geometric_verification ? 0 : ((*chunk_no)++ & 1);
     DeviceBuffer &dcorr = cb ? m->d_corr_alt : m->d_corr;
-    if (m->copied_used[cb]) OSFM_HIP_CHECK(hipEventSynchronize(m->ev_copied[cb]));      // before a reserve may free it
+    // before a reserve may free it -- and before the host block of this list buffer, whose upload lies in front of
+    // that copy, is refilled (with verification the chunk before this one has ended with a wait for the stream)
+    if (m->copied_used[cb]) OSFM_HIP_CHECK(hipEventSynchronize(m->ev_copied[cb]));
     OSFM_RETURN_IF(dcorr.reserve((size_t)chunk_corr * 8));
-    OSFM_HIP_CHECK(hipMemcpyAsync(m->d_m12_off.ptr, h.m12_off.data(), n * 8, hipMemcpyHostToDevice, s));
-    OSFM_HIP_CHECK(hipMemcpyAsync(m->d_corr_off.ptr, h.corr_off.data(), n * 8, hipMemcpyHostToDevice, s));
-    OSFM_HIP_CHECK(hipMemcpyAsync(m->d_len12.ptr, h.len12.data(), n * 4, hipMemcpyHostToDevice, s));
-    OSFM_HIP_CHECK(hipMemcpyAsync(m->d_keep_pair.ptr, h.keep.data(), n, hipMemcpyHostToDevice, s));
-    launch_compact_pairs(n, m->out.as<int32_t>(), m->d_m12_off.as<int64_t>(),
-        m->d_len12.as<int32_t>(), m->d_corr_off.as<int64_t>(), m->d_keep_pair.as<uint8_t>(),
-        dcorr.as<int32_t>(), s);
+    const CompactLayout cl = compact_layout((size_t)n);
+    OSFM_RETURN_IF(m->d_compact[cb].reserve(cl.bytes));
+    OSFM_RETURN_IF(m->h_compact[cb].reserve(cl.bytes));
+    char *hp = m->h_compact[cb].ptr, *dp = m->d_compact[cb].as<char>();
+    memcpy(hp + cl.m12_off, h.m12_off.data(), (size_t)n * 8);
+    memcpy(hp + cl.corr_off, h.corr_off.data(), (size_t)n * 8);
+    memcpy(hp + cl.len12_off, h.len12.data(), (size_t)n * 4);
+    memcpy(hp + cl.keep_off, h.keep.data(), (size_t)n);
+    OSFM_HIP_CHECK(hipMemcpyAsync(dp, hp, cl.bytes, hipMemcpyHostToDevice, cs));
+    launch_compact_pairs(n, m->out.as<int32_t>(), reinterpret_cast<const int64_t *>(dp + cl.m12_off),
+        reinterpret_cast<const int32_t *>(dp + cl.len12_off), reinterpret_cast<const int64_t *>(dp + cl.corr_off),
+        reinterpret_cast<const uint8_t *>(dp + cl.keep_off), dcorr.as<int32_t>(), cs);
     OSFM_HIP_CHECK(hipGetLastError());
     if (!o.geometric_verification) {
-        OSFM_HIP_CHECK(hipEventRecord(m->ev_compact[cb], s));
-        OSFM_HIP_CHECK(hipStreamWaitEvent(m->copy_stream, m->ev_compact[cb], 0));
+        if (cs != m->copy_stream) {
+            OSFM_HIP_CHECK(hipEventRecord(m->ev_compact[cb], cs));
+            OSFM_HIP_CHECK(hipStreamWaitEvent(m->copy_stream, m->ev_compact[cb], 0));
+        }
         OSFM_HIP_CHECK(hipMemcpyAsync(corr + 2 * written, dcorr.ptr, (size_t)chunk_corr * 8,
             hipMemcpyDeviceToHost, m->copy_stream));
         OSFM_HIP_CHECK(hipEventRecord(m->ev_copied[cb], m->copy_stream));
@@ -218,6 +224,8 @@ int match_all_single(osfm_matcher *m, const osfm_pair *pairs, int num_pairs, osf
     bool overflow = false;
     {
         const int bs = full_batch_size(m->views, o, full_idx.size());
+        const char *slices_env = getenv("OSFM_POST_SLICES");
+        const int post_slices_env = slices_env ? atoi(slices_env) : 0;      // 0: default_post_slices of the part
         int chunk_no = 0;
         std::vector<osfm_pair> chunk;
         ChunkLists h;
@@ -233,31 +241,52 @@ int match_all_single(osfm_matcher *m, const osfm_pair *pairs, int num_pairs, osf
             // (the largest part of the largest call announced: what the work arrays are sized for from the first call on)
             if (m->expect_pairs > 0)
                 full_mode.expect = std::min<int>(full_batch_size(m->views, o, (size_t)m->expect_pairs), m->expect_pairs);
-            OSFM_RETURN_IF(run_batch(m, chunk.data(), n, full_mode, &res));
-            lap("matched");
-            // ---- keep / reject by count ----
-            h.m12_off.assign(n, 0); h.corr_off.assign(n, 0); h.len12.assign(n, 0); h.keep.assign(n, 0);
+            // ---- keep / reject by count, compact ----
+            // of the pairs [k0, k1) of the chunk, whose counts are in res; the compaction on stream cs
             int64_t chunk_corr = 0;
-            for (int k = 0; k < n; ++k) {
-                const int p = full_idx[start + k];
-                osfm_pair_result &r = results[p];
-                r.num_matches = res.counts[k];
-                if (res.counts[k] < min_matches) { r.status = OSFM_PAIR_REJECTED_COUNT; continue; }
-                r.status = OSFM_PAIR_MATCHED;
-                r.offset = written + chunk_corr;
-                h.keep[k] = 1;
-                h.m12_off[k] = res.plans[k].off12;
-                h.len12[k] = res.plans[k].len12;
-                h.corr_off[k] = chunk_corr;
-                chunk_corr += res.counts[k];
-            }
-            if (!o.geometric_verification && written + chunk_corr > capacity) overflow = true;
-            // ---- compact ----
-            // With verification the pre-RANSAC lists are device scratch (d_corr) that the
-            // RANSAC jobs of THIS chunk read: they are built whatever the state of the
-            // caller's buffer; only the copies to the host stop after an overflow.
-            if (chunk_corr > 0 && (o.geometric_verification || !overflow))
-                OSFM_RETURN_IF(compact_chunk(m, h, n, chunk_corr, corr, written, &chunk_no));
+            auto emit = [&](int k0, int k1, hipStream_t cs) -> int {
+                const int ns = k1 - k0;
+                h.m12_off.assign(ns, 0); h.corr_off.assign(ns, 0); h.len12.assign(ns, 0); h.keep.assign(ns, 0);
+                chunk_corr = 0;
+                for (int k = k0; k < k1; ++k) {
+                    const int p = full_idx[start + k];
+                    osfm_pair_result &r = results[p];
+                    r.num_matches = res.counts[k];
+                    if (res.counts[k] < min_matches) { r.status = OSFM_PAIR_REJECTED_COUNT; continue; }
+                    r.status = OSFM_PAIR_MATCHED;
+                    r.offset = written + chunk_corr;
+                    h.keep[k - k0] = 1;
+                    h.m12_off[k - k0] = res.plans[k].off12;
+                    h.len12[k - k0] = res.plans[k].len12;
+                    h.corr_off[k - k0] = chunk_corr;
+                    chunk_corr += res.counts[k];
+                }
+                if (!o.geometric_verification && written + chunk_corr > capacity) overflow = true;
+                // With verification the pre-RANSAC lists are device scratch (d_corr) that the
+                // RANSAC jobs of THIS chunk read: they are built whatever the state of the
+                // caller's buffer; only the copies to the host stop after an overflow.
+                if (chunk_corr > 0 && (o.geometric_verification || !overflow))
+                    OSFM_RETURN_IF(compact_chunk(m, h, ns, chunk_corr, corr, written, &chunk_no, cs));
+                return OSFM_OK;
+            };
+            // Nothing is matched behind a call's last part, so its lists would leave the device with nothing else
+            // running: its post-work runs in slices (OSFM_POST_SLICES, read per call; 1: one sequence as for every
+            // other part), and a slice's lists are compacted and copied on the copy stream while the main stream
+            // finishes the next slice.  With verification the RANSAC jobs want the whole chunk's lists: no slices.
+            SliceSink sink;
+            sink.requested = post_slices_env;
+            sink.on_slice = [&](int k0, int k1) -> int {
+                OSFM_RETURN_IF(emit(k0, k1, m->copy_stream));
+                written += chunk_corr;
+                return OSFM_OK;
+            };
+            const bool last = end == full_idx.size();
+            bool sliced = false;
+            OSFM_RETURN_IF(run_batch(m, chunk.data(), n, full_mode, &res,
+                last && !o.geometric_verification ? &sink : nullptr, &sliced));
+            lap("matched");
+            if (sliced) continue;
+            OSFM_RETURN_IF(emit(0, n, m->stream));
             // ---- verify ----
             if (o.geometric_verification && chunk_corr > 0)
                 OSFM_RETURN_IF(verify_chunk(m, pairs, full_idx.data() + start, n, res.counts, h, chunk_corr, results, corr,

@@ -14,6 +14,54 @@
 
 #include "match_plan.h"
 
+namespace osfm {
+
+// Page-locked host memory that only grows (contents not kept); whoever grows it has waited for the transfer that
+// still reads it.  Freed with the matcher.
+struct PinnedBlock {
+    char *ptr = nullptr;
+    size_t bytes = 0;
+    PinnedBlock() = default;
+    PinnedBlock(const PinnedBlock &) = delete;
+    PinnedBlock &operator=(const PinnedBlock &) = delete;
+    ~PinnedBlock() { pinned_free(ptr, bytes); }
+    int reserve(size_t need)
+    {
+        if (need <= bytes) return OSFM_OK;
+        pinned_free(ptr, bytes);
+        ptr = nullptr; bytes = 0;
+        const size_t want = need + need / 8 + 256;
+        void *p = nullptr;
+        OSFM_HIP_CHECK(pinned_alloc(&p, want, hipHostMallocDefault));
+        ptr = static_cast<char *>(p); bytes = want;
+        return OSFM_OK;
+    }
+};
+
+// An event without timing, made on first use and destroyed with the matcher.
+struct LazyEvent {
+    hipEvent_t e = nullptr;
+    LazyEvent() = default;
+    LazyEvent(const LazyEvent &) = delete;
+    LazyEvent &operator=(const LazyEvent &) = delete;
+    ~LazyEvent() { event_destroy(e); }
+    int make()
+    {
+        if (!e) OSFM_HIP_CHECK(event_create(&e, false));
+        return OSFM_OK;
+    }
+};
+
+// What run_batch hands out per slice of a batch whose post-work runs in slices (match_plan.h: post_slice_bounds):
+// the pairs [p0, p1) of the batch are finished and their counts are in res->counts.  The main stream is busy
+// with the later slices meanwhile.
+struct SliceSink {
+    int requested = 1;          // slices asked for (<= 0: the default for the batch's size)
+    std::function<int(int p0, int p1)> on_slice;
+};
+
+}  // namespace osfm
+
 struct osfm_matcher {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -28,16 +76,27 @@ struct osfm_matcher {
     std::mutex up_mu;
 
     // scratch (grow-only)
-    osfm::DeviceBuffer d_problems[2], rowparts, colparts, out, keep, mark_off[2], counts[2];
-    osfm::DeviceBuffer exact_items, exact_count, stage_in, flags;
-    osfm::DeviceBuffer rs_count, rs_items;      // bucketed rescoring of the SIFT finish: bucket fill counts, items
-    osfm::DeviceBuffer sp_parts, sp_col, d_spjobs;      // match_special_kernel: row results, column results, job list
-    osfm::DeviceBuffer clock_probe;
+    osfm::DeviceBuffer rowparts, colparts, out, keep;
+    osfm::DeviceBuffer exact_items, stage_in, flags;
+    osfm::DeviceBuffer rs_items;                // bucketed rescoring of the SIFT finish: the buckets' items
+    osfm::DeviceBuffer sp_parts, sp_col;        // match_special_kernel: row results, column results
+    // Per batch one upload, one memset, one read-back (match_plan.h: StagingLayout, ControlLayout):
+    //   d_batch    problems, mark offsets and special jobs, uploaded in one copy from h_batch.  Every batch ends
+    //              with a wait for the stream, so the upload that read h_batch is over before it is refilled (or
+    //              regrown); planning a batch while the one before it runs would need a second block or an event.
+    //   d_control  every counter the kernels add to, cleared by one memset; its head comes back into h_read in one
+    //              copy.  h_read is read by the host behind the wait for that copy and before the next one is queued.
+    osfm::DeviceBuffer d_batch, d_control;
+    osfm::PinnedBlock h_batch, h_read;
+    osfm::LazyEvent ev_slice[osfm::kMaxPostSlices];      // behind the count read-back of a slice
     osfm::BatchPlan plan;                 // run_batch's plan (under mu): its vectors keep their memory from batch to batch
     osfm::DeviceBuffer zero_tile;         // kTileCols blank descriptors: what the correction-free tile loop prefetches past a segment's end
     int special_max = 512;                // views with more special descriptors take the per-view operand forms
     int expect_pairs = 0;                 // osfm_match_expect_pairs: the largest call to come (work arrays sized for it)
-    osfm::DeviceBuffer d_m12_off, d_len12, d_corr_off, d_keep_pair, d_corr;
+    // the four per-pair arrays of the compaction in one block (CompactLayout), uploaded in one copy from the host
+    // block of the list buffer the compaction fills: ev_copied of that list buffer lies behind the upload too
+    osfm::DeviceBuffer d_compact[2], d_corr;
+    osfm::PinnedBlock h_compact[2];
     // osfm_match_all without verification: the lists of chunk k leave the device on a copy stream while
     // chunk k + 1 is matched (two list buffers alternate)
     osfm::DeviceBuffer d_corr_alt;
@@ -100,7 +159,10 @@ namespace osfm {
 
 // match_batch.hip
 int check_view(const osfm_matcher *m, int v, const char *what);
-int run_batch(osfm_matcher *m, const osfm_pair *pairs, int num_pairs, const BatchMode &mode, BatchResult *res);
+// sink: the post-work of the batch in slices (exhaustive matching only), each handed to sink->on_slice when its
+// counts have arrived; without it, or with one slice, the batch is one sequence and on_slice is not called
+int run_batch(osfm_matcher *m, const osfm_pair *pairs, int num_pairs, const BatchMode &mode, BatchResult *res,
+    const SliceSink *sink = nullptr, bool *sliced = nullptr);
 void reset_stats(osfm_matcher *m);
 
 // match_views.hip

@@ -108,6 +108,46 @@ int plan_batch(const std::vector<ViewData> &views, const osfm_match_options &opt
 int batch_size_for(const std::vector<ViewData> &views, const osfm_match_options &o, bool lowres);
 int full_batch_size(const std::vector<ViewData> &views, const osfm_match_options &o, size_t n_full);
 
+// The post-work of a call's last part (finish, rescore, exact scan, cross-check, count read-back) is issued per
+// slice of its pairs, so that a slice's lists leave the device while the next slice is finished.
+// requested <= 0: default_post_slices(pairs).  bounds: the slices are the pairs [bounds[k], bounds[k + 1]);
+// at most min(pairs, kMaxPostSlices) of them, none empty.  Returns their number (0 for no pairs).
+constexpr int kMaxPostSlices = 64;
+int default_post_slices(int pairs);
+int post_slice_bounds(int pairs, int requested, std::vector<int> *bounds);
+
+// One device block per batch for everything that is zeroed before the batch runs, cleared by one memset; its
+// first read_bytes (the exact-scan counters of every slice and type, the clock probe, the counts of both types)
+// come back in one copy.  The rescore bucket counts lie behind them.
+struct ControlLayout {
+    size_t exact_off = 0;          // int32[2][kMaxPostSlices]: exact-scan items of (type, slice)
+    size_t probe_off = 0;          // unsigned long long[2]
+    size_t counts_off[2] = {0, 0}; // int32[problems of the type]
+    size_t read_bytes = 0;
+    size_t rs_off = 0;             // int32[rs_buckets]
+    size_t bytes = 0;
+};
+ControlLayout control_layout(size_t np_sift, size_t np_surf, int64_t rs_buckets);
+
+// One block for everything a batch uploads (staged page-locked on the host, one copy): the problems and the
+// mark offsets of both types, the jobs of the two special kernels.
+struct StagingLayout {
+    size_t probs_off[2] = {0, 0};  // MatchProblem[problems of the type]
+    size_t mark_off[2] = {0, 0};   // int64[2 * problems of the type]
+    size_t sp_off = 0;             // SpecialJob[spjobs], then SpecialJob[spjobs_wide] back to back
+    size_t bytes = 0;
+};
+StagingLayout staging_layout(size_t np_sift, size_t np_surf, size_t spjobs, size_t spjobs_wide);
+
+// The four per-pair arrays of the list compaction in one block.
+struct CompactLayout {
+    size_t m12_off = 0, corr_off = 0;      // int64[n]
+    size_t len12_off = 0;                  // int32[n]
+    size_t keep_off = 0;                   // uint8[n]
+    size_t bytes = 0;
+};
+CompactLayout compact_layout(size_t n);
+
 void deal_pairs_lpt(const std::vector<ViewData> &views, int num_shards, const osfm_pair *pairs, const std::vector<int> &cand,
     std::vector<std::vector<int>> *owner);
 

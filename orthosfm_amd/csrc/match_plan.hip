@@ -286,6 +286,72 @@ int full_batch_size(const std::vector<ViewData> &views, const osfm_match_options
     return bs;
 }
 
+// A slice adds four or five launches and a read-back and hides the copy of the slices before it (63 MB of lists per
+// 1225 pairs of 20 000 features).  Neither number here is settled by measurement: one run of the headline step per
+// value put 2, 3 and 4 slices 0.4 - 0.8 ms below the parent and within noise of one another
+// (profiles/r11_step_ab.txt), and the 96 pairs below which a part stays one sequence are an estimate (a slice's
+// launches against the copy time of some tens of pairs).
+int default_post_slices(int pairs) { return pairs >= 96 ? 3 : 1; }
+
+int post_slice_bounds(int pairs, int requested, std::vector<int> *bounds)
+{
+    bounds->clear();
+    if (pairs <= 0) return 0;
+    if (requested <= 0) requested = default_post_slices(pairs);
+    const int n = std::max(1, std::min(std::min(requested, pairs), kMaxPostSlices));
+    for (int k = 0; k <= n; ++k) bounds->push_back((int)((int64_t)pairs * k / n));      // n <= pairs: strictly rising
+    return n;
+}
+
+namespace {
+constexpr size_t kBlockAlign = 64;
+size_t take(size_t *at, size_t bytes)
+{
+    const size_t off = *at;
+    *at = (off + bytes + kBlockAlign - 1) / kBlockAlign * kBlockAlign;
+    return off;
+}
+}  // namespace
+
+ControlLayout control_layout(size_t np_sift, size_t np_surf, int64_t rs_buckets)
+{
+    ControlLayout l;
+    size_t at = 0;
+    l.exact_off = take(&at, (size_t)2 * kMaxPostSlices * sizeof(int32_t));
+    l.probe_off = take(&at, 2 * sizeof(unsigned long long));
+    l.counts_off[0] = take(&at, np_sift * sizeof(int32_t));
+    l.counts_off[1] = take(&at, np_surf * sizeof(int32_t));
+    l.read_bytes = at;
+    l.rs_off = take(&at, (size_t)std::max<int64_t>(rs_buckets, 0) * sizeof(int32_t));
+    l.bytes = at;
+    return l;
+}
+
+StagingLayout staging_layout(size_t np_sift, size_t np_surf, size_t spjobs, size_t spjobs_wide)
+{
+    StagingLayout l;
+    size_t at = 0;
+    l.probs_off[0] = take(&at, np_sift * sizeof(MatchProblem));
+    l.probs_off[1] = take(&at, np_surf * sizeof(MatchProblem));
+    l.mark_off[0] = take(&at, np_sift * 2 * sizeof(int64_t));
+    l.mark_off[1] = take(&at, np_surf * 2 * sizeof(int64_t));
+    l.sp_off = take(&at, (spjobs + spjobs_wide) * sizeof(SpecialJob));
+    l.bytes = std::max(at, kBlockAlign);
+    return l;
+}
+
+CompactLayout compact_layout(size_t n)
+{
+    CompactLayout l;
+    size_t at = 0;
+    l.m12_off = take(&at, n * sizeof(int64_t));
+    l.corr_off = take(&at, n * sizeof(int64_t));
+    l.len12_off = take(&at, n * sizeof(int32_t));
+    l.keep_off = take(&at, n);
+    l.bytes = std::max(at, kBlockAlign);
+    return l;
+}
+
 // Longest processing time first on N1 * N2 over the pairs `cand` (ascending pair indices); ties go to the lower
 // shard.  Equal work everywhere degenerates to round robin, as in distributed.py.
 void deal_pairs_lpt(const std::vector<ViewData> &views, int num_shards, const osfm_pair *pairs, const std::vector<int> &cand,
