@@ -47,7 +47,10 @@ OSFM_API const char *osfm_last_error(void);
  * binds keep the earlier, shorter layout.  Such a caller still runs correctly, so the version is still 102.  The
  * consensus filter (osfm_ba_consensus, osfm_scene_filter_consensus and their structs) is new entries only, and so
  * are the observation refinement (osfm_refine_* and its structs), the dense plane sweep (osfm_dense_*) and the
- * depth-map meshes (osfm_dense_set_map, osfm_dense_mesh_*, osfm_dense_download_mesh and their structs). */
+ * depth-map meshes (osfm_dense_set_map, osfm_dense_mesh_*, osfm_dense_download_mesh and their structs).  The
+ * slanted-plane refinement (osfm_dense_refine_*, osfm_dense_download_refined and their structs) is new entries too;
+ * osfm_dense_mesh_options.reserved, which the defaults set to 0, is now called refined_normals: same size, same offset,
+ * and 0 is what it was. */
 #define OSFM_ABI_VERSION 102
 OSFM_API int osfm_version(void);
 /* Number of visible HIP devices (0 when there is none). */
@@ -1711,7 +1714,8 @@ typedef struct osfm_dense_mesh_options {
     int32_t confidence_iterations;      /* 3: confidence min(distance to the mesh border, K) / K; 0: all 1; 0..max */
     int32_t min_island;                 /* 0: 4-connected components of fewer solid pixels are cleared; >= 0 */
     int32_t use_fused;                  /* 0; 1: a pixel is solid only if the last fusion left it OK or DUPLICATE */
-    int32_t reserved;
+    int32_t refined_normals;            /* 0; not 0: a vertex whose pixel is OSFM_DENSE_REFINE_REFINED takes the normal of
+                                         * osfm_dense_refine_view; every other vertex, and everything else, as with 0 */
 } osfm_dense_mesh_options;
 OSFM_API int osfm_dense_mesh_options_default(osfm_dense_mesh_options *opts);
 /* The shape of the kernels as built: the tile of the component labelling, the largest confidence_iterations.  Any
@@ -1736,7 +1740,8 @@ typedef struct osfm_dense_mesh_stats {
  * are the pixels a triangle names, row-major.  Repeats to the bit.  num_vertices, num_triangles, stats may be NULL.
  *   OSFM_E_ARG      null handle; dd_factor negative or not finite, confidence_iterations outside 0..max, min_island < 0
  *   OSFM_E_RANGE    view outside [0, num_views)
- *   OSFM_E_STATE    the view has no depth map; use_fused without a fusion
+ *   OSFM_E_STATE    the view has no depth map; use_fused without a fusion; refined_normals on a view whose map was not
+ *                   refined (osfm_dense_refine_view)
  *   OSFM_E_NUMERIC  the labelling ran into its iteration bound (65536 steps of one walk: a defect, or a component that
  *                   winds through more tile-local pieces than that in one chain; reported instead of a hang): no mesh
  * None of them writes an output. */
@@ -1753,6 +1758,72 @@ OSFM_API int osfm_dense_download_mesh(osfm_dense *d, int64_t capacity_vertices, 
  * (a point set, as fssrecon reads it).  NULL: normals zeros, rgb zeros, confidence ones, scale zeros. */
 OSFM_API int osfm_dense_mesh_write(const char *path, int64_t num_vertices, const double *points, const double *normals,
     const uint8_t *rgb, const float *confidence, const double *scale, int64_t num_triangles, const int32_t *triangles);
+
+/* ---- Slanted-plane refinement of a depth map: sub-step depth, a depth gradient and a normal per pixel ---------------
+ * An opt-in stage between sweep and fusion; tests/dense_refine_restatement.py is the definition, DESIGN.md
+ * "Slanted-plane refinement" describes it.  Every OSFM_DENSE_OK pixel x of the view's map, at depth z0, gets the local
+ * depth model z(x + u) = z + zx ux + zy uy.  With G = A_s B_r, g = t_s - G t_r, e = A_s d_r its window lands in source
+ * s at (G x + g + z e) + (G + e (zx, zy)) u: one affine map per pixel and source, exact for a planar patch.
+ * Gauss-Newton runs over (z, zx, zy), shared by the sources, and a gain and a bias per source, on the residuals
+ * gain_s W_s(u) + bias_s - T(u): T the reference window (grey values, u integer in [-radius, radius]^2), W_s the
+ * bilinear samples of source s.  A source counts when every sample of its window at (z0, 0, 0) lies in
+ * [0, width - 1] x [0, height - 1]; the set is fixed there.  From the samples on everything is double arithmetic in a
+ * fixed order: a call repeats to the bit and a pixel's result does not depend on any other pixel.
+ *
+ * One status per pixel; the first test that fails, in time, decides: */
+#define OSFM_DENSE_REFINE_NOT_OK 0          /* the sweep's status is not OSFM_DENSE_OK: untouched */
+#define OSFM_DENSE_REFINE_REFINED 1
+#define OSFM_DENSE_REFINE_OUTSIDE 2         /* the reference window leaves its image; fewer than min_sources sources count; a
+                                             * counting source's window leaves its image at an iteration or at the end */
+#define OSFM_DENSE_REFINE_ILL_CONDITIONED 3 /* the gain/bias block of a source is singular, or a pivot of the Cholesky factor
+                                             * of the diagonally scaled 3 x 3 normal matrix is below min_pivot */
+#define OSFM_DENSE_REFINE_NOT_CONVERGED 4   /* max_iterations steps without |dz| <= eps dz and radius (|dzx| + |dzy|) <= eps dz */
+#define OSFM_DENSE_REFINE_REJECT_SHIFT 5    /* |z - z0| > max_shift steps */
+#define OSFM_DENSE_REFINE_REJECT_SLOPE 6    /* a singular value of a counting source's G + e (zx, zy) outside [1 / max_deform, max_deform] */
+#define OSFM_DENSE_REFINE_REJECT_SCORE 7    /* the mean over the counting sources of the zero-mean normalised correlation of T
+                                             * and W_s at the end is below min_score, or below what it was at the start */
+#define OSFM_DENSE_REFINE_NUM_STATUS 8
+
+typedef struct osfm_dense_refine_options {
+    int32_t radius;           /* 3: the sweep's window; 1..7 */
+    int32_t min_sources;      /* 2; 1..8 */
+    int32_t max_iterations;   /* 10; 1..100 */
+    int32_t reserved;
+    double eps;               /* 1e-3 depth steps of the view; > 0 */
+    double max_shift;         /* 1.5 depth steps: the sweep's best index is within one step of its own peak; >= 0 */
+    double max_deform;        /* 2.0, as osfm_refine_options; >= 1 */
+    double min_score;         /* 0.8, the sweep's; -1..1 */
+    double min_pivot;         /* 0.035 (how it was measured: DESIGN.md); 0 < min_pivot < 1 */
+} osfm_dense_refine_options;
+OSFM_API int osfm_dense_refine_options_default(osfm_dense_refine_options *opts);
+
+typedef struct osfm_dense_refine_stats {
+    int64_t status_count[OSFM_DENSE_REFINE_NUM_STATUS];    /* pixels per status */
+    int64_t iterations;                                     /* Gauss-Newton steps taken, summed */
+    int64_t samples;                                        /* warped samples taken (window x source evaluations) */
+    double device_ms;                                       /* the kernel, by device events */
+} osfm_dense_refine_stats;
+
+/* Refines the map of `view` (swept, or uploaded by osfm_dense_set_map) as it stands, against sources[num_sources]: the
+ * pixels that come out REFINED take the new depth and, as their score, the mean correlation at the end; all others
+ * keep the map's depth and score.  The handle keeps, per pixel, the status, the gradient (zx, zy) in depth per pixel
+ * and the unit normal cross(b1 + zy d, b0 + zx d) / |.| (b0, b1 the columns of B_r; n . d < 0: towards the camera, the
+ * sign of the meshes' vertex normals); gradient and normal are NaN where the status is not REFINED.  The sweep's own
+ * status plane does not change, so the fusion and the meshes see the same solid pixels; the view still counts as
+ * swept, and an earlier fusion and an earlier mesh of it are gone, as after a sweep.  Refining a view twice refines
+ * the refined depths.  opts NULL: the defaults.  Outputs, each [height][width] rows of the view's image and each may be
+ * NULL: depth, gradient [.][2], normal [.][3], score, rstatus -- the whole planes as they stand after the call.
+ *   OSFM_E_ARG    null handle or sources, options out of range, num_sources outside 1..max_sources or below
+ *                 min_sources, a source equal to view or repeated
+ *   OSFM_E_RANGE  a view id outside [0, num_views)
+ *   OSFM_E_STATE  no cameras, no map of the view, or a source without an image
+ * None of them writes anything. */
+OSFM_API int osfm_dense_refine_view(osfm_dense *d, int view, int num_sources, const int32_t *sources,
+    const osfm_dense_refine_options *opts, double *depth, double *gradient, double *normal, float *score, uint8_t *rstatus,
+    osfm_dense_refine_stats *stats);
+/* What the last osfm_dense_refine_view of the view left on the device; each may be NULL.  OSFM_E_RANGE: the view;
+ * OSFM_E_STATE: the view's map was not refined (a new image, new cameras or a new map drop the planes). */
+OSFM_API int osfm_dense_download_refined(osfm_dense *d, int view, double *gradient, double *normal, uint8_t *rstatus);
 
 #ifdef __cplusplus
 }

@@ -367,7 +367,7 @@ class DenseStats(C.Structure):
 
 class DenseMeshOptions(C.Structure):
     """osfm_dense_mesh_options."""
-    _fields_ = [("dd_factor", C.c_double)] + [(n, C.c_int32) for n in ("confidence_iterations", "min_island", "use_fused", "reserved")]
+    _fields_ = [("dd_factor", C.c_double)] + [(n, C.c_int32) for n in ("confidence_iterations", "min_island", "use_fused", "refined_normals")]
 
 
 MESH_VERTEX_SIMPLE, MESH_VERTEX_BORDER, MESH_VERTEX_COMPLEX = range(3)
@@ -382,6 +382,28 @@ class DenseMeshStats(C.Structure):
 
     def counters(self) -> dict:
         return {n: int(getattr(self, n)) for n, t in self._fields_ if t is C.c_int64}
+
+
+class DenseRefineOptions(C.Structure):
+    """osfm_dense_refine_options."""
+    _fields_ = [(n, C.c_int32) for n in ("radius", "min_sources", "max_iterations", "reserved")] + \
+               [(n, C.c_double) for n in ("eps", "max_shift", "max_deform", "min_score", "min_pivot")]
+
+
+DENSE_REFINE_STATUS = ("not_ok", "refined", "outside", "ill_conditioned", "not_converged", "reject_shift", "reject_slope", "reject_score")
+(DENSE_REFINE_NOT_OK, DENSE_REFINE_REFINED, DENSE_REFINE_OUTSIDE, DENSE_REFINE_ILL_CONDITIONED, DENSE_REFINE_NOT_CONVERGED,
+ DENSE_REFINE_REJECT_SHIFT, DENSE_REFINE_REJECT_SLOPE, DENSE_REFINE_REJECT_SCORE) = range(8)
+
+
+class DenseRefineStats(C.Structure):
+    """osfm_dense_refine_stats."""
+    _fields_ = [("status_count", C.c_int64 * len(DENSE_REFINE_STATUS)), ("iterations", C.c_int64), ("samples", C.c_int64),
+                ("device_ms", C.c_double)]
+
+    def counters(self) -> dict:
+        d = {n: int(self.status_count[i]) for i, n in enumerate(DENSE_REFINE_STATUS)}
+        d["iterations"] = int(self.iterations)
+        return d
 
 
 # every symbol include/osfm_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -427,6 +449,7 @@ EXPORTS = [
     "osfm_dense_download_status", "osfm_dense_download_cloud", "osfm_dense_cloud_write",
     "osfm_dense_set_map", "osfm_dense_mesh_options_default", "osfm_dense_mesh_limits", "osfm_dense_mesh_view",
     "osfm_dense_download_mesh", "osfm_dense_mesh_write",
+    "osfm_dense_refine_options_default", "osfm_dense_refine_view", "osfm_dense_download_refined",
 ]
 
 # osfm_track_feature as a numpy record (32 bytes, no padding)
@@ -520,6 +543,10 @@ lib.osfm_dense_download_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
 lib.osfm_dense_download_cloud.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.osfm_dense_cloud_write.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p]
 lib.osfm_dense_set_map.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double]
+lib.osfm_dense_refine_options_default.argtypes = [C.POINTER(DenseRefineOptions)]
+lib.osfm_dense_refine_view.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(DenseRefineOptions)] + [C.c_void_p] * 5 + \
+                                      [C.POINTER(DenseRefineStats)]
+lib.osfm_dense_download_refined.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.osfm_dense_mesh_options_default.argtypes = [C.POINTER(DenseMeshOptions)]
 lib.osfm_dense_mesh_limits.argtypes = [C.POINTER(C.c_int32)] * 3
 lib.osfm_dense_mesh_view.argtypes = [C.c_void_p, C.c_int, C.POINTER(DenseMeshOptions), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -670,6 +697,17 @@ def default_dense_mesh_options(**kw) -> DenseMeshOptions:
     for k, v in kw.items():
         if not hasattr(o, k):
             raise TypeError(f"osfm_dense_mesh_options has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def default_dense_refine_options(**kw) -> DenseRefineOptions:
+    """osfm_dense_refine_options_default with the given fields replaced."""
+    o = DenseRefineOptions()
+    check(lib.osfm_dense_refine_options_default(C.byref(o)))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"osfm_dense_refine_options has no field {k!r}")
         setattr(o, k, v)
     return o
 

@@ -99,6 +99,8 @@ int osfm_dense_create(int device, int num_views, osfm_dense **out)
     d->grey.resize(V); d->depth.resize(V); d->score.resize(V); d->status.resize(V); d->final_status.resize(V);
     d->images.assign(V, refine::Image{nullptr, 0, 0});
     d->geo.resize(V);
+    d->refine_status.resize(V); d->refine_gradient.resize(V); d->refine_normal.resize(V);
+    d->refined.assign(V, 0);
     d->swept.assign(V, 0);
     d->dz.assign(V, 0.0);
     OSFM_RETURN_IF(d->table.reserve(V * sizeof(dense::FuseView)));

@@ -1,5 +1,5 @@
-// The handle behind osfm_dense, shared by the entries of the sweep and the fusion (dense_api.hip) and those of the
-// depth-map meshes (mesh_api.hip).
+// The handle behind osfm_dense, shared by the entries of the sweep and the fusion (dense_api.hip), those of the
+// slanted-plane refinement (dense_refine_api.hip) and those of the depth-map meshes (mesh_api.hip).
 #pragma once
 #include <vector>
 
@@ -12,6 +12,10 @@ struct osfm_dense {
     std::vector<osfm::DeviceBuffer> grey;          // float32 [h][w] per view
     std::vector<osfm::refine::Image> images;
     std::vector<osfm::DeviceBuffer> depth, score, status, final_status;      // per swept view
+    // of osfm_dense_refine_view (dense_refine_api.hip), per refined view: status [h][w], gradient [h][w][2], normal [h][w][3]
+    std::vector<osfm::DeviceBuffer> refine_status, refine_gradient, refine_normal;
+    std::vector<uint8_t> refined;
+    osfm::DeviceBuffer refine_counters;
     std::vector<osfm::dense::ViewGeo> geo;
     std::vector<uint8_t> swept;
     std::vector<double> dz;
@@ -34,6 +38,7 @@ namespace dense {
 inline void drop_map(osfm_dense *d, int view)
 {
     d->swept[view] = 0;
+    d->refined[view] = 0;
     d->fused = false;
     if (d->mesh_view == view) d->mesh_view = -1;
 }

@@ -66,7 +66,7 @@ int osfm_dense_mesh_options_default(osfm_dense_mesh_options *o)
     o->confidence_iterations = 3;
     o->min_island = 0;
     o->use_fused = 0;
-    o->reserved = 0;
+    o->refined_normals = 0;
     return OSFM_OK;
 }
 
@@ -94,12 +94,18 @@ int osfm_dense_mesh_view(osfm_dense *d, int view, const osfm_dense_mesh_options 
     OSFM_RETURN_IF(check_mesh_view(d, view, "osfm_dense_mesh_view"));
     if (!d->cameras || !d->swept[view]) { set_error("osfm_dense_mesh_view: view %d has no depth map", view); return OSFM_E_STATE; }
     if (o.use_fused && !d->fused) { set_error("osfm_dense_mesh_view: use_fused without a fusion (osfm_dense_fuse)"); return OSFM_E_STATE; }
+    if (o.refined_normals && !d->refined[view]) {
+        set_error("osfm_dense_mesh_view: refined_normals, and the map of view %d was not refined (osfm_dense_refine_view)", view);
+        return OSFM_E_STATE;
+    }
 
     OSFM_HIP_CHECK(hipSetDevice(d->device));
     mesh::View v;
     std::memset(&v, 0, sizeof(v));
     v.depth = d->depth[view].as<double>(); v.status = d->status[view].as<uint8_t>();
     v.final_status = o.use_fused ? d->final_status[view].as<uint8_t>() : nullptr;
+    v.refine_status = o.refined_normals ? d->refine_status[view].as<uint8_t>() : nullptr;
+    v.refine_normal = o.refined_normals ? d->refine_normal[view].as<double>() : nullptr;
     v.w = d->images[view].w; v.h = d->images[view].h;
     v.geo = d->geo[view];
     const size_t n = (size_t)v.w * v.h;                        // at most 2^28: the counts fit the scans' int32

@@ -26,6 +26,8 @@ struct View {
     const double *depth;          // [h][w]
     const uint8_t *status;        // the sweep's
     const uint8_t *final_status;  // the fusion's, or null
+    const uint8_t *refine_status; // of the slanted-plane refinement, or null: its REFINED pixels take refine_normal [h][w][3]
+    const double *refine_normal;
     int32_t w, h;
     dense::ViewGeo geo;
 };

@@ -359,10 +359,11 @@ __global__ __launch_bounds__(256) void mesh_emit_kernel(View v, const uint8_t *_
         }
     }
     const int64_t slot = vscan[i];
+    const bool stored = v.refine_status && v.refine_status[i] == OSFM_DENSE_REFINE_REFINED;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         mesh.points[3 * slot + j] = P[4][j];
-        mesh.normals[3 * slot + j] = flat ? 0.0 : sum[j] / nn;
+        mesh.normals[3 * slot + j] = stored ? v.refine_normal[3 * i + j] : flat ? 0.0 : sum[j] / nn;
     }
     mesh.scale[slot] = edges / (double)count;
     const int d = min((int)dist[i], iterations);

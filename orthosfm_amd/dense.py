@@ -102,6 +102,21 @@ class DepthMap:
 
 
 @dataclass
+class RefinedMap:
+    """What osfm_dense_refine_view leaves of a view's map; the arrays are None with download=False."""
+    depth: np.ndarray         # float64 [h, w]: the map after the call (refined where the status is DENSE_REFINE_REFINED)
+    gradient: np.ndarray      # float64 [h, w, 2]: depth per pixel along x and y; NaN where not refined
+    normal: np.ndarray        # float64 [h, w, 3]: unit, towards the camera; NaN where not refined
+    score: np.ndarray         # float32 [h, w]: the map's after the call
+    status: np.ndarray        # uint8 [h, w]: capi.DENSE_REFINE_*
+    stats: capi.DenseRefineStats
+
+    @property
+    def refined(self):
+        return self.status == capi.DENSE_REFINE_REFINED
+
+
+@dataclass
 class Cloud:
     points: np.ndarray        # float64 [N, 3]
     view: np.ndarray          # int32 [N]
@@ -165,6 +180,29 @@ class DenseStereo(_Handle):
                                              int(num_depths), C.byref(o), p(res.depth), p(res.score), p(res.status),
                                              C.byref(res.stats)))
         return res
+
+    def refine(self, view: int, sources, download=True, **options) -> RefinedMap:
+        """osfm_dense_refine_view: slanted-plane refinement of the view's map, in place; options: the fields of
+        osfm_dense_refine_options.  download=False leaves everything on the device (refined_planes() fetches it)."""
+        o = capi.default_dense_refine_options(**options)
+        sources = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        shape = self._shape[int(view)] if 0 <= int(view) < self.num_views else None
+        res = RefinedMap(None, None, None, None, None, capi.DenseRefineStats())
+        if download and shape is not None:
+            res.depth, res.gradient, res.normal = np.zeros(shape), np.zeros(shape + (2,)), np.zeros(shape + (3,))
+            res.score, res.status = np.zeros(shape, np.float32), np.zeros(shape, np.uint8)
+        p = lambda a: a.ctypes.data if a is not None else None
+        capi.check(capi.lib.osfm_dense_refine_view(self._h, int(view), sources.shape[0], sources.ctypes.data, C.byref(o), p(res.depth),
+                                                   p(res.gradient), p(res.normal), p(res.score), p(res.status), C.byref(res.stats)))
+        return res
+
+    def refined_planes(self, view: int):
+        """osfm_dense_download_refined: (gradient [h, w, 2], normal [h, w, 3], status [h, w]) of the view's last refine()."""
+        shape = self._shape[int(view)] if 0 <= int(view) < self.num_views else None
+        shape = shape if shape is not None else (1, 1)
+        gradient, normal, status = np.zeros(shape + (2,)), np.zeros(shape + (3,)), np.zeros(shape, np.uint8)
+        capi.check(capi.lib.osfm_dense_download_refined(self._h, int(view), gradient.ctypes.data, normal.ctypes.data, status.ctypes.data))
+        return gradient, normal, status
 
     def fuse(self, **options) -> Cloud:
         """osfm_dense_fuse and osfm_dense_download_cloud."""

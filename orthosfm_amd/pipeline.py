@@ -1371,6 +1371,8 @@ class DenseResult:
     meshes: list = None       # densify(meshes=True): per view a dense.ViewMesh, or None for a view that was not swept
     pset: "PointSet" = None   # densify(meshes=True): the vertices of all meshes with confidence > 0
     mesh_ms: float = 0.0
+    refined: list = None      # densify(refine=...): per view a dense.RefinedMap (arrays with keep_maps=True), or None
+    refine_ms: float = 0.0
 
 
 @dataclass
@@ -1392,13 +1394,16 @@ def _pixel_colours(image, pixel):
 
 
 def densify(images, model, cam_params, points, visibility, device=0, views=None, keep_maps=False, max_sources=4, meshes=False,
-            mesh_options=None, **options):
+            mesh_options=None, refine=False, **options):
     """A dense point cloud from adjusted cameras: every view in `views` (None: all) is swept against the sources
     dense.plan_view picks among them, over the depth range of its own sparse points, then all maps are fused.
     images: uint8 [h, w] or [h, w, 3] per view; cam_params [V, 7]; points [M, 3+]; visibility: per view the indices
     of the sparse points it sees (what the depth range is taken from).  options: fields of osfm_dense_options.
     meshes=True: every swept view is also meshed after the fusion (use_fused = 1; mesh_options: further fields of
     osfm_dense_mesh_options), and the result carries the meshes and their point set.
+    refine=True, or a dict of fields of osfm_dense_refine_options: every swept view's map is refined against its
+    plan's sources before the fusion (dense.DenseStereo.refine; radius, min_sources and min_score are the sweep's unless
+    the dict names them), and the meshes take the refined normals where there are any.  False changes nothing.
     This step has no counterpart in the reference."""
     from . import dense
     V = len(images)
@@ -1422,10 +1427,22 @@ def densify(images, model, cam_params, points, visibility, device=0, views=None,
             sweep_ms += m.stats.device_ms
             if keep_maps:
                 maps[v] = m
+        refined, refine_ms = None, 0.0
+        if refine:
+            ro = {k: options[k] for k in ("radius", "min_sources", "min_score") if k in options}
+            if isinstance(refine, dict):
+                ro.update(refine)
+            refined = [None] * V
+            for v in views:
+                if plans[v] is not None:
+                    refined[v] = ds.refine(v, plans[v].sources, download=keep_maps, **ro)
+                    refine_ms += refined[v].stats.device_ms
         cloud = ds.fuse(**options)
         view_meshes = None
         if meshes:
             mo = dict(mesh_options or {}, use_fused=1)
+            if refine:
+                mo["refined_normals"] = 1
             view_meshes = [ds.mesh(v, **mo) if plans[v] is not None else None for v in range(V)]
             for m in view_meshes:
                 if m is not None:
@@ -1439,6 +1456,7 @@ def densify(images, model, cam_params, points, visibility, device=0, views=None,
             rgb[sel] = px[:, None] if im.ndim == 2 else px[:, :3]
     res = DenseResult(cloud.points, rgb, cloud.view, cloud.pixel, plans, maps, cloud.stats.counters(), sweep_ms,
                       cloud.stats.device_ms)
+    res.refined, res.refine_ms = refined, refine_ms
     if meshes:
         parts = [(m, m.confidence > 0.0) for m in view_meshes if m is not None]
         cat = lambda pick, shape, dt: np.concatenate([pick(m, k) for m, k in parts]) if parts else np.zeros(shape, dt)
